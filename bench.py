@@ -8,7 +8,15 @@ semantics. One step = one verify pass over the whole batch, inputs and the accep
 vector resident in HBM (no PCIe in the timed region; the PCIe-inclusive rate is
 reported separately as `end_to_end`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--cpu-sample S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up the corpus, warms up, times the K steps and prints the headline line (value,
+ms_per_step, the accept-vector check). `--full` adds every other leg to the line: the stage
+tables and roofline (extra steps after the timed region), the golden parity hashes, the sustained
+and adversarial rates, the PCIe-inclusive rates, config 4, config 5, the WAL check, the CPU
+baselines and the footprint; the per-leg switches (--no-e2e, --cpu-sample 0, ...) apply to it.
+`--dump-outputs DIR` writes what the last timed step left in its caller's buffers (the status
+vector, and on the batch path the equation flag) as DIR/<name>.npy in float32.
 
 N > 1: one rank per GPU under torch.distributed.run. Launched bare (`bench.py --gpus N`,
 no WORLD_SIZE), the script starts that launcher itself as a child process before any
@@ -242,6 +250,13 @@ def main():
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1 << 20, help="signatures per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="config2: after the timed steps, also measure and check every other leg of the line "
+                         "(stage tables and roofline, golden parity, sustained, adversarial, end-to-end, config 4, "
+                         "config 5, WAL, CPU baselines, footprint); the switches below apply to these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config2: write the last timed step's outputs (status vector; batch path: the equation "
+                         "flag) as DIR/<name>.npy in float32 (ranks > 0 of a multi-GPU run: <name>_rank<r>.npy)")
     ap.add_argument("--cpu-sample", type=int, default=1 << 20, help="0 disables the CPU baseline")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--streams", type=int, default=3, help="batch path: streams the steps rotate over (3: profiles/r05/c2_streams_slots.txt)")
@@ -282,6 +297,10 @@ def main():
                     help="skip the WAL replay-check rate (row f4) in the default line")
     ap.add_argument("--wal-entries", type=int, default=1 << 20, help="WAL entries (config-4 blocks) per GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload != "config2":
+        ap.error("--dump-outputs writes the config2 workload's outputs only")
     from mysticeti_amd.dist import launch_ranks, needs_launch
 
     if needs_launch(args.gpus):
@@ -300,7 +319,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # the CPU baselines run on rank 0 of a one-GPU run only: the N > 1 lines of a scaling run
     # report the GPUs alone (and finish sooner); config 5's GPU-vs-CPU latency leg keeps its CPU side
-    cpu_legs = args.cpu_sample > 0 and world == 1
+    cpu_legs = args.full and args.cpu_sample > 0 and world == 1
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     import torch
     # one GPU per rank; a rehearsal with more ranks than GPUs (e.g. 2 ranks on a 1-GPU box) shares
@@ -319,8 +338,8 @@ def main():
     import mysticeti_amd as M
     from mysticeti_amd.dist import all_ranks_ok, footprint, hbm_sample, rss_mark, shard_range, timed_region
 
-    def progress(what):  # one stderr line per leg (a long run shows it is alive)
-        if rank == 0:
+    def progress(what, always=False):  # one stderr line per leg of a --full run (a long run shows it is alive)
+        if rank == 0 and (args.full or always):
             print(f"bench: {what} ({time.strftime('%H:%M:%S')})", file=sys.stderr, flush=True)
 
     eng = M.Engine(devices=(local_rank,))
@@ -372,7 +391,8 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    hbm_sample(torch, dev, "config2")
+    if args.full:
+        hbm_sample(torch, dev, "config2")
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev_side = [torch.cuda.Event() for _ in range(nstreams)]
 
@@ -391,11 +411,20 @@ def main():
             ev1.record(streams[0])
         torch.cuda.synchronize(dev)
 
-    progress("corpus ready, timed region")
+    progress("corpus ready, timed region", always=True)
     elapsed = timed_region(timed_step, args.steps, close_and_sync, dist)
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # device time per step on the launch streams
+    last = (args.warmup + args.steps - 1) % nstreams  # the last timed step's output buffers
+    if args.dump_outputs:
+        # before any later leg launches on these buffers again
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = f"_rank{rank}" if rank else ""
+        np.save(os.path.join(args.dump_outputs, f"status{suffix}.npy"), d_status[last].cpu().numpy().astype(np.float32))
+        if args.path == "batch":
+            np.save(os.path.join(args.dump_outputs, f"batch_ok{suffix}.npy"),
+                    d_ok[last].cpu().numpy().astype(np.float32))
     stage_ms = {}
-    if args.path == "batch":
+    if args.full and args.path == "batch":
         # the as-run stage table: HIP events around every stage of a few more steps on the same
         # alternating streams, after the timed region (the events stay out of `value`)
         eng.stage_times(reset=True)
@@ -411,7 +440,7 @@ def main():
     # for `value`), so the dominant kernel's duration matches the single-stream rocprof trace
     # (profiles/<round>/, tools/gpu.sh trace:c2s1).
     iso_ms = {}
-    if args.path == "batch" and nstreams > 1:
+    if args.full and args.path == "batch" and nstreams > 1:
         eng.stage_times(reset=True)
         eng.set_stage_timing(True)
         for _ in range(3):
@@ -420,18 +449,19 @@ def main():
         tot, calls = eng.stage_times()
         eng.set_stage_timing(False)
         iso_ms = {k: v / calls[k] for k, v in tot.items() if calls[k]}
-    batch_ok = all(int(x.item()) == 1 for x in d_ok) if args.path == "batch" else None
+    used = min(nstreams, state["i"])  # fewer steps than streams leave the later buffers unwritten
+    batch_ok = all(int(x.item()) == 1 for x in d_ok[:used]) if args.path == "batch" else None
 
-    status = d_status[(args.warmup + args.steps - 1) % nstreams].cpu().numpy()
+    status = d_status[last].cpu().numpy()
     accepted = int((status == 0).sum())
     if bad_idx is None:
-        ok = accepted == n and all((x.cpu().numpy() == 0).all() for x in d_status)
+        ok = accepted == n and all((x.cpu().numpy() == 0).all() for x in d_status[:used])
     else:
         want = np.zeros(n, np.uint8)
         want[bad_idx.cpu().numpy()] = 1
-        ok = all((x.cpu().numpy() == want).all() for x in d_status)
+        ok = all((x.cpu().numpy() == want).all() for x in d_status[:used])
     parity = None
-    if rank == 0 and n == (1 << 20) and bad_idx is None:
+    if args.full and rank == 0 and n == (1 << 20) and bad_idx is None:
         gold = json.load(open(os.path.join(ROOT, "tests", "golden", "batch_config2.json")))
         parity = hashlib.sha256(status.tobytes()).hexdigest() == gold["sha256_status"] and \
             hashlib.sha256(d_sig.cpu().numpy().tobytes()).hexdigest() == gold["sha256_sig"]
@@ -442,7 +472,7 @@ def main():
     if args.path == "batch":
         # headline roofline: k_bv_prep's real work over its single-stream time (the stage
         # events of the post-run one-stream steps; the 2-stream as-run time is reported beside)
-        kern, kern_ms = "k_bv_prep", iso_ms.get("prep", stage_ms["prep"])
+        kern, kern_ms = "k_bv_prep", iso_ms.get("prep", stage_ms.get("prep"))
         w_kern = slots(F_PREP, W_SHA512_OPS + W_BLAKE2B_OPS)
         w_step = slots(F_BATCH_STEP, W_SHA512_OPS + W_BLAKE2B_OPS)
         kdesc = (f"{F_PREP} field ops x {FIELD_MACS} MACs x {MAC_SLOTS} slots + SHA-512 {W_SHA512_OPS} + "
@@ -451,12 +481,29 @@ def main():
         kern, kern_ms = "k_verify", kernel_ms
         w_kern = w_step = slots(F_SINGLE, W_SHA512_OPS)
         kdesc = f"{F_SINGLE} field ops x {FIELD_MACS} MACs x {MAC_SLOTS} slots + SHA-512 {W_SHA512_OPS} ops"
-    achieved = n / (kern_ms * 1e-3) * w_kern
-    traffic, traffic_src = pmc_traffic(kern)
+    roofline = None  # (--full: the dominant kernel's time comes from the extra stage-timed steps)
+    if args.full:
+        achieved = n / (kern_ms * 1e-3) * w_kern
+        traffic, traffic_src = pmc_traffic(kern)
+        roofline = {"bound": "valu", "achieved": round(achieved / 1e12, 3), "peak": round(PEAK_VALU_OPS / 1e12, 2),
+                    "unit": "TOP/s", "frac": round(achieved / PEAK_VALU_OPS, 4), "traffic": traffic,
+                    "traffic_source": traffic_src, "kernel": kern, "kernel_ms": round(kern_ms, 4),
+                    "kernel_ms_source": "HIP events on the launch stream around k_bv_prep, 3 post-run steps "
+                                        "on ONE stream (compare profiles/<round>/kernel_stats_config2_1stream.csv)",
+                    "kernel_ms_as_run": round(stage_ms.get("prep", kern_ms), 4) if stage_ms else None,
+                    "frac_label": "real work of the dominant kernel: its field ops and hashes at the full-rate "
+                                  "INT32 VALU peak",
+                    "work_per_sig": kdesc,
+                    "frac_8d": {"value": round(value / world * W8D_SECONDS_PER_SIG, 4),
+                                "label": "SURVEY.md 8(d) fixed work (W_verify = 3,200 field ops x 64 MACs at the "
+                                         "v_mad_u64_u32 peak 39.3 T/s + W_sha512 6,000 ops at 78.6 T/s) x "
+                                         "value; exceeds 1 because the batch algorithm does ~726 field ops "
+                                         "per signature, not the single-verify 3,200"},
+                    "stage_ms_one_stream": {k: round(v, 4) for k, v in iso_ms.items()} if iso_ms else None}
 
     # sustained rate: >= 5 repeats of >= 2 s each (DVFS settles), median
     sustained = None
-    if args.sustain_repeats > 0:
+    if args.full and args.sustain_repeats > 0:
         per = max(args.steps, int(math.ceil(args.sustain_seconds / max(elapsed / args.steps, 1e-4))))
         vals = []
         for _ in range(args.sustain_repeats):
@@ -472,7 +519,7 @@ def main():
     # dense failures send them to the single path; with three streams in flight the policy
     # sees a batch's flags about three batches later)
     adversarial = None
-    if args.path == "batch" and args.adversarial and not args.corrupt:
+    if args.full and args.path == "batch" and args.adversarial and not args.corrupt:
         adversarial = {}
         rng = np.random.default_rng(2025)
         for name, idx in (("one_bad_per_batch", np.array([n // 3])),
@@ -518,7 +565,7 @@ def main():
     progress("adversarial done")
     # PCIe-inclusive rates (host buffers through the C ABI)
     e2e = None
-    if rank == 0 and not args.no_e2e:
+    if args.full and rank == 0 and not args.no_e2e:
         # PCIe-inclusive: host buffers in, accept vector out, through the C ABI
         pk_h, sig_h = d_pk.cpu().numpy(), d_sig.cpu().numpy()
 
@@ -579,7 +626,7 @@ def main():
     # config 4 (the largest workload): whole-block verification of HBM-resident 100-validator
     # blocks, measured in the same run (bench_blocks.config4_measure)
     cfg4 = None
-    if args.config4 and args.path == "batch" and not args.corrupt:
+    if args.full and args.config4 and args.path == "batch" and not args.corrupt:
         import bench_blocks
 
         cfg4 = bench_blocks.config4_measure(eng, torch, local_rank, world, dist, n=args.config4_batch,
@@ -592,7 +639,7 @@ def main():
     progress("config4 done")
     # f4: the WAL replay check over an HBM-resident WAL of config-4 blocks (bench_wal.wal_measure)
     walr = None
-    if args.wal and args.path == "batch" and not args.corrupt:
+    if args.full and args.wal and args.path == "batch" and not args.corrupt:
         import bench_wal
 
         walr = bench_wal.wal_measure(eng, torch, local_rank, world, dist, n=args.wal_entries,
@@ -605,7 +652,7 @@ def main():
     # mv_verify_blocks on host buffers, GPU and CPU in the same run (bench_blocks.config5_measure);
     # rank 0 only (the host CPU legs would otherwise compete across ranks)
     cfg5 = None
-    if args.config5 and args.path == "batch" and not args.corrupt and rank == 0:
+    if args.full and args.config5 and args.path == "batch" and not args.corrupt and rank == 0:
         import bench_blocks
 
         eng.set_batch_groups(args.groups)
@@ -621,7 +668,7 @@ def main():
         cpu = cpu_baseline(d_pk.cpu().numpy(), d_sig.cpu().numpy(), msg_h, min(args.cpu_sample, n))
         rss_mark("cpu_baseline")
     # per-rank peak host RSS and HBM in use (all ranks; the line must hold at 8 ranks per node)
-    fp = footprint(rank, dist)
+    fp = footprint(rank, dist) if args.full else None
     out = None
     if rank == 0:
         out = {
@@ -641,21 +688,7 @@ def main():
             "config": {"workload": "config2: 1,048,576 independent Ed25519 (ZIP-215) signatures over 32-byte "
                                    "block digests per GPU", "batch_per_gpu": n, "global_batch": n * world,
                        "parallelism": f"shard-per-gpu x{world}, no collective"},
-            "roofline": {"bound": "valu", "achieved": round(achieved / 1e12, 3), "peak": round(PEAK_VALU_OPS / 1e12, 2),
-                         "unit": "TOP/s", "frac": round(achieved / PEAK_VALU_OPS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src, "kernel": kern, "kernel_ms": round(kern_ms, 4),
-                         "kernel_ms_source": "HIP events on the launch stream around k_bv_prep, 3 post-run steps "
-                                             "on ONE stream (compare profiles/<round>/kernel_stats_config2_1stream.csv)",
-                         "kernel_ms_as_run": round(stage_ms.get("prep", kern_ms), 4) if stage_ms else None,
-                         "frac_label": "real work of the dominant kernel: its field ops and hashes at the full-rate "
-                                       "INT32 VALU peak",
-                         "work_per_sig": kdesc,
-                         "frac_8d": {"value": round(value / world * W8D_SECONDS_PER_SIG, 4),
-                                     "label": "SURVEY.md 8(d) fixed work (W_verify = 3,200 field ops x 64 MACs at the "
-                                              "v_mad_u64_u32 peak 39.3 T/s + W_sha512 6,000 ops at 78.6 T/s) x "
-                                              "value; exceeds 1 because the batch algorithm does ~726 field ops "
-                                              "per signature, not the single-verify 3,200"},
-                         "stage_ms_one_stream": {k: round(v, 4) for k, v in iso_ms.items()} if iso_ms else None},
+            "roofline": roofline,
             "pipeline": {"device_ms_per_step": round(kernel_ms, 4),
                          "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()} if stage_ms else None,
                          "achieved_TOPs": round(value / world * w_step / 1e12, 3),
@@ -673,9 +706,10 @@ def main():
             "end_to_end": e2e,
             "footprint": {"per_rank": fp, "note": "host_rss_peak_GB: getrusage ru_maxrss (pinned staging included); "
                                                   "hbm_peak_GB: largest hipMemGetInfo total - free seen after each "
-                                                  "leg's warm-up (device-wide)"},
+                                                  "leg's warm-up (device-wide)"} if fp else None,
             "correct": bool(ok),
             "path": args.path,
+            "full": args.full,
             "batch_equation_held": batch_ok,
             "parity_sha256": parity,
         }

@@ -9,9 +9,9 @@
 #
 #   tests[:K]        pytest -m gpu (K: a -k expression)
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's default line: bench.py --gpus 1 --steps 20 --warmup 5
+#   bench            the whole line: bench.py --gpus 1 --steps 20 --warmup 5 --full
 #   bench100         the default line at 100 steps (steady-state cross-check of `bench`)
-#   c2[:ARGS]        config-2 line only (no legs); ARGS (comma-separated) appended
+#   c2[:ARGS]        config-2 line with its stage tables and roofline (--full, no other legs); ARGS (comma-separated) appended
 #   c4[:ARGS]        --workload config4 (2^21 blocks, 20 steps); ARGS appended
 #   c5               --workload config5
 #   wal              --workload wal
@@ -20,7 +20,7 @@
 #   abc4:V[:ARGS]    the same on config 4
 #   env:K=V          export K=V for the tasks that follow (SUF=x: later bench outputs are named <task>x.json)
 #   e2e[:ENV=V,..]   tools/e2e_probe.py (pinned end-to-end signatures) under these settings
-#   benchtrace       the driver's bench command under rocprofv3 --kernel-trace --stats
+#   benchtrace       the `bench` task's command under rocprofv3 --kernel-trace --stats
 #   h2d              tools/h2d_probe.py: pinned H2D rates (whole arrays, chunks, two streams)
 #   e2etrace         tools/e2e_probe.py with two callers (MV_PROBE_TWO) under kernel + memory-copy trace
 #   trace:W          rocprofv3 --kernel-trace --stats of workload W in {c2, c2s1, c2single, c4, c4s1, c5, wal}
@@ -37,7 +37,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 
-C2ONLY="--cpu-sample 0 --no-e2e --sustain-repeats 0 --no-adversarial --no-config4 --no-wal --no-config5"
+C2ONLY="--full --cpu-sample 0 --no-e2e --sustain-repeats 0 --no-adversarial --no-config4 --no-wal --no-config5"
 declare -A W=(
   [c2]="python bench.py --steps 5 --warmup 1 $C2ONLY"
   [c2s1]="python bench.py --steps 5 --warmup 1 --streams 1 $C2ONLY"
@@ -86,10 +86,10 @@ for T in "$@"; do
       run 150 "$OUT/smoke.log" python -c "import __graft_entry__ as g; g.smoke(); print('__SMOKE_OK__')"
       tail -1 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench$SUF.json" 2> "$OUT/bench$SUF.err" || { echo "bench FAILED"; tail -8 "$OUT/bench$SUF.err"; exit 1; }
+      timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench$SUF.json" 2> "$OUT/bench$SUF.err" || { echo "bench FAILED"; tail -8 "$OUT/bench$SUF.err"; exit 1; }
       line "$OUT/bench$SUF.json" ;;
     bench100)
-      timeout -k 10 900 python bench.py --steps 100 --warmup 5 > "$OUT/bench100$SUF.json" 2> "$OUT/bench100$SUF.err" || { echo "bench100 FAILED"; tail -8 "$OUT/bench100$SUF.err"; exit 1; }
+      timeout -k 10 900 python bench.py --steps 100 --warmup 5 --full > "$OUT/bench100$SUF.json" 2> "$OUT/bench100$SUF.err" || { echo "bench100 FAILED"; tail -8 "$OUT/bench100$SUF.err"; exit 1; }
       line "$OUT/bench100$SUF.json" ;;
     c2)
       timeout -k 10 300 python bench.py --steps 600 --warmup 10 $C2ONLY ${arg//,/ } > "$OUT/c2$SUF.json" 2> "$OUT/c2$SUF.err" || { echo "c2 FAILED"; tail -8 "$OUT/c2$SUF.err"; exit 1; }
@@ -104,7 +104,7 @@ for T in "$@"; do
       timeout -k 10 600 python bench.py --workload wal --steps 20 --warmup 2 --cpu-sample 0 > "$OUT/wal$SUF.json" 2> "$OUT/wal$SUF.err" || { echo "wal FAILED"; tail -8 "$OUT/wal$SUF.err"; exit 1; }
       line "$OUT/wal$SUF.json" ;;
     gpus2)
-      timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-config5 --host-fed-blocks 0 --cpu-sample 0 --no-e2e --sustain-repeats 1 > "$OUT/gpus2$SUF.json" 2> "$OUT/gpus2$SUF.err" || { echo "gpus2 FAILED"; tail -8 "$OUT/gpus2$SUF.err"; exit 1; }
+      timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-config5 --host-fed-blocks 0 --cpu-sample 0 --no-e2e --sustain-repeats 1 > "$OUT/gpus2$SUF.json" 2> "$OUT/gpus2$SUF.err" || { echo "gpus2 FAILED"; tail -8 "$OUT/gpus2$SUF.err"; exit 1; }
       line "$OUT/gpus2$SUF.json" ;;
     ab|abc4)
       V=${arg%%:*}
@@ -134,8 +134,8 @@ for T in "$@"; do
     e2e)  # e2e[:ENV=V,ENV=V]: the pinned end-to-end probe under these environment settings
       (export ${arg//,/ }; timeout -k 10 300 python tools/e2e_probe.py) >> "$OUT/e2e.log" 2>&1 || { echo "e2e FAILED"; tail -5 "$OUT/e2e.log"; exit 1; }
       tail -1 "$OUT/e2e.log" ;;
-    benchtrace)  # the driver's bench command under rocprofv3 --kernel-trace --stats (the roofline's source)
-      run 900 "$OUT/benchtrace.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/benchtrace" -o run -- python bench.py --gpus 1 --steps 20 --warmup 5
+    benchtrace)  # the `bench` task's command under rocprofv3 --kernel-trace --stats (the roofline's source)
+      run 900 "$OUT/benchtrace.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/benchtrace" -o run -- python bench.py --gpus 1 --steps 20 --warmup 5 --full
       grep -E '^\{' "$OUT/benchtrace.log" | tail -1 | cut -c1-200
       python3 tools/trace_top.py "$OUT/benchtrace" ;;
     h2d)  # tools/h2d_probe.py: pinned H2D rates in the streamed path's copy shapes

@@ -7,8 +7,8 @@ d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 out = []
 m = lambda v: round(v / 1e6, 2)
 if "config4" in d or d.get("unit") == "sigs/s":
-    out.append(f"c2 {m(d['value'])} M/s ok={d['correct']} frac={d.get('roofline', {}).get('frac')} "
-               f"prep_ms={d.get('roofline', {}).get('kernel_ms')}")
+    out.append(f"c2 {m(d['value'])} M/s ok={d['correct']} frac={(d.get('roofline') or {}).get('frac')} "
+               f"prep_ms={(d.get('roofline') or {}).get('kernel_ms')}")
     if d.get("sustained"):
         out.append(f"sust {m(d['sustained']['median'])}")
     if d.get("end_to_end"):
