@@ -301,7 +301,9 @@ mv_status mv_stage_times(mv_ctx* ctx, double* ms /* MV_NSTAGES or NULL */, uint6
  * changes a verdict, digest or crc. */
 mv_status mv_set_option(mv_ctx* ctx, const char* name, int64_t value);
 mv_status mv_get_option(mv_ctx* ctx, const char* name, int64_t* value);
-/* Runs field/scalar primitive `op` on n lane inputs (16 words each) -> 16 words each (host buffers). */
+/* Runs field/scalar primitive `op` on n lane inputs (16 words each) -> 16 words each (host buffers).
+ * Ops >= 64 are the raw-limb field and point test hooks: 64 words in and 64 words out per lane
+ * (the row layout is documented at k_selftest_wide in kernels.hip). */
 mv_status mv_selftest(mv_ctx* ctx, int op, const uint32_t* in, uint32_t n, uint32_t* out);
 
 #ifdef __cplusplus

@@ -58,6 +58,7 @@ STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "has
           "wal_crc"]
 FLAG_NO_BATCH, FLAG_NO_COMB, FLAG_HOST_PARSE, FLAG_NO_ONLINE = 1, 2, 4, 8
 BATCH_MIN = 4096
+SELFTEST_WIDE_OP = 64  # mv_selftest ops from here on use 64-word rows
 
 
 class MvError(RuntimeError):
@@ -457,7 +458,14 @@ class Engine:
 
     # ---- diagnostics ----
     def selftest(self, op: int, words: np.ndarray) -> np.ndarray:
-        w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32)).reshape(-1, 16)
+        """Ops 0..63 take and return 16-word rows; ops >= SELFTEST_WIDE_OP (raw-limb field and point
+        functions, kernels.hip k_selftest_wide) take and return 64-word rows: `words` must be
+        two-dimensional with that width."""
+        width = 64 if op >= SELFTEST_WIDE_OP else 16
+        w = np.asarray(words, dtype=np.uint32)
+        if width == 64 and (w.ndim != 2 or w.shape[1] != 64):
+            raise ValueError(f"selftest op {op} takes rows of 64 words, got shape {w.shape}")
+        w = np.ascontiguousarray(w).reshape(-1, width)
         out = np.zeros_like(w)
         self._check(self.lib.mv_selftest(self.ctx, op, _p(w), w.shape[0], _p(out)), "mv_selftest")
         return out

@@ -3104,11 +3104,16 @@ mv_status mv_selftest(mv_ctx* ctx, int op, const uint32_t* in, uint32_t n, uint3
   std::lock_guard<std::mutex> lk(ctx->mu);
   Device& dev = ctx->devs[0];
   HIPCHK(ctx, hipSetDevice(dev.id));
-  HIPCHK(ctx, dev.bytes.ensure(64 * (size_t)n + 64));
-  HIPCHK(ctx, dev.out2.ensure(64 * (size_t)n + 64));
-  HIPCHK(ctx, hipMemcpyAsync(dev.bytes.p, in, 64 * (size_t)n, hipMemcpyHostToDevice, dev.stream));
-  HIPCHK(ctx, mvk::launch_selftest(op, dev.bytes.as<uint32_t>(), n, dev.btab.p, dev.out2.as<uint32_t>(), dev.stream));
-  HIPCHK(ctx, hipMemcpyAsync(out, dev.out2.p, 64 * (size_t)n, hipMemcpyDeviceToHost, dev.stream));
+  const bool wide = op >= mvk::SELFTEST_WIDE_OP;
+  const size_t row = wide ? 256 : 64;  // bytes per row, in and out
+  HIPCHK(ctx, dev.bytes.ensure(row * n + 64));
+  HIPCHK(ctx, dev.out2.ensure(row * n + 64));
+  HIPCHK(ctx, hipMemcpyAsync(dev.bytes.p, in, row * n, hipMemcpyHostToDevice, dev.stream));
+  if (wide)
+    HIPCHK(ctx, mvk::launch_selftest_wide(op, dev.bytes.as<uint32_t>(), n, dev.out2.as<uint32_t>(), dev.stream));
+  else
+    HIPCHK(ctx, mvk::launch_selftest(op, dev.bytes.as<uint32_t>(), n, dev.btab.p, dev.out2.as<uint32_t>(), dev.stream));
+  HIPCHK(ctx, hipMemcpyAsync(out, dev.out2.p, row * n, hipMemcpyDeviceToHost, dev.stream));
   HIPCHK(ctx, hipStreamSynchronize(dev.stream));
   return MV_OK;
 }

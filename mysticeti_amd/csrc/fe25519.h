@@ -35,7 +35,10 @@ struct fe {
   uint32_t v[9];
 };
 
-// ---- normalisation: carry pass, limbs < 2^32 in -> N out ----
+// ---- normalisation: serial carry pass, limbs <= 2^32 - 8 in -> N out ----
+// Each limb takes its neighbour's carry (at most 7) before it is split, so a limb above
+// 2^32 - 8 can wrap. The largest limb a call site produces is fe_sub's a + (bias - b)
+// < 2^30 + 2^24 + 2^31 (fe_addn: < 2^31 + 2^25).
 MV_DEV void fe_normalize(fe& r) {
   uint32_t c;
 #pragma unroll

@@ -9,6 +9,7 @@
 //   (BLAKE2b: blake2b_quad.hip for small calls, blake2b_lane.hip at batch size; the
 //   launch_blake2b / launch_block_hash entry points below route between them)
 //   k_selftest       field / scalar primitives for the parity tests
+//   k_selftest_wide  field and point functions on raw limbs (the limb-bound contract's tests)
 //
 // The verify kernel is INT32-VALU bound: HBM traffic is 128 B of
 // input per signature plus the per-lane variable-base tables (2 x 9 cached points,
@@ -27,6 +28,8 @@
 #include "scalar25519.h"
 #include "tables.h"
 #include "comb.h"
+#include "quad25519.h"
+#include "pt_r16.h"
 
 namespace mv {
 
@@ -512,6 +515,251 @@ __global__ void __launch_bounds__(64) k_selftest(int op, const uint32_t* __restr
   for (int i = 0; i < 16; i++) out[16 * (size_t)gid + i] = y[i];
 }
 
+// Field and point functions on RAW limbs (ops >= 64, 64-word rows): the tests of the limb-bound
+// contract of fe25519.h and of the point formulas (tests/test_gpu_limb_bounds.py,
+// tests/test_gpu_points.py). Each op calls the production function directly.
+//   in : words 0..35   four operands a, b, c, d as raw limbs (9 words each, used unmasked)
+//        word  36      parameter
+//        words 40..47  encoding of P, words 48..55 encoding of Q (point ops)
+//   out: words 0..35   raw limbs of the result (field ops: words 0..8; point ops: X, Y, Z, T)
+//        word  36      flags
+//        words 40..47  the canonical value (fe_to_words) / the compressed point
+//        words 48..56  point additions: raw limbs of cached(Q).YpX as used
+// Field ops (flags only for 72: bit 0 fe_is_zero(a), 1 fe_is_negative(a), 2 fe_eq(a, b)):
+//   64 fe_mul(a, b)   65 fe_sq(a)   66 fe_mul_small(a, parameter)   67 fe_add   68 fe_addn
+//   69 fe_sub   70 fe_neg(a)   71 fe_normalize(a)   72 fe_canon(a), out words 40..47 fe_to_words(a)
+//   73 fe_sqn(a, parameter)   74 fe_invert(a)   75 feq_mul   76 feq_sqn(a, parameter)
+//   77 fer_mul   78 fer_sqn(a, parameter)   79 r4::carry(a)   80 r4::addn   81 r4::sub
+// Point ops: P = (a, b, c, d) raw when parameter bit 11 is set, else the decoded P encoding;
+// Q is the decoded Q encoding (parameter bits 8..9 = 0), P itself (1) or P's (Y, X, T, Z) (2).
+// Parameter bits 0..7: P is doubled that many times first; bit 12: Q = p3_neg(Q) first;
+// bit 10: the table entry of Q is negated (cached_cneg / precomp_cneg; quad and row forms: -Q);
+// bit 13 (96..98): words 0..35 are the p1p1 result's raw limbs instead of the p3's.
+//   96 p2_dbl + p1p1_to_p3   97 p3_to_cached + p3_add_cached   98 p3_add_precomp (Q with Z = 1)
+//   99 qp_dbl   100 qp_add   101 qp_in_torsion (flag bit 3; the result is P)
+//   102 r4::dbl   103 r4::addp
+// flags: bit 0 p3_is_identity(result), bit 1 / 2 P / Q decoded.
+// As in k_selftest, every lane of a quad (75, 76, 99..101), of a 16-lane row (77..81) or of a
+// wave (102, 103) must carry the same input row; all 64 lanes stay active.
+__global__ void __launch_bounds__(64) k_selftest_wide(int op, const uint32_t* __restrict__ in, uint32_t n,
+                                                      uint32_t* __restrict__ out) {
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t* x = in + 64 * (size_t)(gid < n ? gid : n - 1);
+  fe f[4], extra;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int i = 0; i < 9; i++) f[k].v[i] = x[9 * k + i];
+  const uint32_t param = x[36];
+  const fe a = f[0], b = f[1];
+  uint32_t flags = 0, ow[8];
+  fe_set(extra, 0);
+  if (op < 96) {
+    const int nsq = (int)(param & 0xffu) ? (int)(param & 0xffu) : 1;
+    fe r;
+    fe_set(r, 0);
+    switch (op) {
+      case 64: fe_mul(r, a, b); break;
+      case 65: fe_sq(r, a); break;
+      case 66: fe_mul_small(r, a, param); break;
+      case 67: fe_add(r, a, b); break;
+      case 68: fe_addn(r, a, b); break;
+      case 69: fe_sub(r, a, b); break;
+      case 70: fe_neg(r, a); break;
+      case 71: r = a; fe_normalize(r); break;
+      case 72:
+        fe_canon(r, a);
+        flags = (fe_is_zero(a) ? 1u : 0u) | (fe_is_negative(a) ? 2u : 0u) | (fe_eq(a, b) ? 4u : 0u);
+        break;
+      case 73: fe_sqn(r, a, nsq); break;
+      case 74: fe_invert(r, a); break;
+      case 75: {
+        feq qa, qb, qr;
+        feq_from_fe(qa, a);
+        feq_from_fe(qb, b);
+        feq_mul(qr, qa, qb);
+        fe_from_feq(r, qr);
+        break;
+      }
+      case 76: {
+        feq qa, qr;
+        feq_from_fe(qa, a);
+        feq_sqn(qr, qa, nsq);
+        fe_from_feq(r, qr);
+        break;
+      }
+      case 77: {
+        fer ra, rb, rr;
+        fer_from_fe(ra, a);
+        fer_from_fe(rb, b);
+        fer_mul(rr, ra, rb, r16::consts());
+        fe_from_fer(r, rr);
+        break;
+      }
+      case 78: {
+        fer ra, rr;
+        fer_from_fe(ra, a);
+        fer_sqn(rr, ra, nsq, r16::consts());
+        fe_from_fer(r, rr);
+        break;
+      }
+      case 79: case 80: case 81: {
+        const r16::Consts K = r16::consts();
+        fer ra, rb, rr;
+        fer_from_fe(ra, a);
+        fer_from_fe(rb, b);
+        rr = op == 79 ? r4::carry(ra.v, K) : (op == 80 ? r4::addn(ra, rb, K) : r4::sub(ra, rb, K));
+        fe_from_fer(r, rr);
+        break;
+      }
+      default: break;
+    }
+    if (op == 72) fe_to_words(ow, a);
+    else fe_to_words(ow, r);
+    f[0] = r;
+    fe_set(f[1], 0);
+    fe_set(f[2], 0);
+    fe_set(f[3], 0);
+  } else {
+    const int kdbl = (int)(param & 0xffu);
+    const uint32_t qmode = (param >> 8) & 3u;
+    const bool neg = (param >> 10) & 1u, raw = (param >> 11) & 1u, qneg = (param >> 12) & 1u;
+    p3 P, Q, R;
+    bool okP, okQ;
+    {
+      uint32_t ep[8], eq[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        ep[i] = x[40 + i];
+        eq[i] = x[48 + i];
+      }
+      decompress_x2(P, okP, ep, Q, okQ, eq);
+    }
+    fe_cmov(P.X, f[0], raw);
+    fe_cmov(P.Y, f[1], raw);
+    fe_cmov(P.Z, f[2], raw);
+    fe_cmov(P.T, f[3], raw);
+    {
+      const p3 P0 = P;
+      fe_cmov(Q.X, P0.X, qmode == 1);
+      fe_cmov(Q.Y, P0.Y, qmode == 1);
+      fe_cmov(Q.Z, P0.Z, qmode == 1);
+      fe_cmov(Q.T, P0.T, qmode == 1);
+      fe_cmov(Q.X, P0.Y, qmode == 2);
+      fe_cmov(Q.Y, P0.X, qmode == 2);
+      fe_cmov(Q.Z, P0.T, qmode == 2);
+      fe_cmov(Q.T, P0.Z, qmode == 2);
+    }
+    if (qneg) p3_neg(Q, Q);
+    R = P;
+    switch (op) {
+      case 96: case 97: case 98: {
+        p1p1 t;
+#pragma unroll 1
+        for (int i = 0; i < kdbl; i++) {
+          p3_dbl(t, P);
+          p1p1_to_p3(P, t);
+        }
+        if (op == 96) {
+          p2 h;
+          h.X = P.X; h.Y = P.Y; h.Z = P.Z;
+          p2_dbl(t, h);
+        } else if (op == 97) {
+          cached c;
+          p3_to_cached(c, Q);
+          cached_cneg(c, neg);
+          extra = c.YpX;
+          p3_add_cached(t, P, c);
+        } else {
+          fe d2;
+          fe_const(d2, K_D2);
+          precomp c;  // Q has Z = 1: (y + x, y - x, 2dxy)
+          fe_add(c.ypx, Q.Y, Q.X);
+          fe_sub(c.ymx, Q.Y, Q.X);
+          fe_mul(c.xy2d, Q.T, d2);
+          precomp_cneg(c, neg);
+          extra = c.ypx;
+          p3_add_precomp(t, P, c);
+        }
+        p1p1_to_p3(R, t);
+        if ((param >> 13) & 1u) {  // the completed point itself: ge25519.h's bounds on p1p1
+          R.X = t.X; R.Y = t.Y; R.Z = t.Z; R.T = t.T;
+        }
+        break;
+      }
+      case 99: case 100: case 101: {
+        const uint32_t c = qlane();
+        fe v, w;
+        fe_qsel(v, c, P.X, P.Y, P.Z, P.T);
+        fe_qsel(w, c, Q.X, Q.Y, Q.Z, Q.T);
+        qp_dbl_n(v, kdbl);
+        if (op == 99) {
+          qp_dbl(v);
+        } else if (op == 100) {
+          fe nw;
+          fe_neg(nw, w);
+          fe_cmov(w, nw, neg && (c == 0u || c == 3u));
+          qp_add(v, w);
+        } else {
+          flags |= qp_in_torsion(v) ? 8u : 0u;
+        }
+        fe_qget<0>(R.X, v);
+        fe_qget<1>(R.Y, v);
+        fe_qget<2>(R.Z, v);
+        fe_qget<3>(R.T, v);
+        break;
+      }
+      case 102: case 103: {
+        const r16::Consts K = r16::consts();
+        const uint32_t c = r4::row();
+        fe vf, wf;
+        fe_qsel(vf, c, P.X, P.Y, P.Z, P.T);
+        fe_qsel(wf, c, Q.X, Q.Y, Q.Z, Q.T);
+        fer v, w;
+        fer_from_fe(v, vf);
+        fer_from_fe(w, wf);
+#pragma unroll 1
+        for (int i = 0; i < kdbl; i++) r4::dbl(v, K);
+        if (op == 102) {
+          r4::dbl(v, K);
+        } else {
+          fe d2;
+          fe_const(d2, K_D2);
+          fer d2r, z;
+          fer_from_fe(d2r, d2);
+          z.v = 0;
+          const fer nw = r4::sub(z, w, K);
+          w.v = neg && (c == 0u || c == 3u) ? nw.v : w.v;
+          r4::addp(v, w, d2r, K);
+        }
+        fe_from_fer(R.X, r4::get<0>(v));
+        fe_from_fer(R.Y, r4::get<1>(v));
+        fe_from_fer(R.Z, r4::get<2>(v));
+        fe_from_fer(R.T, r4::get<3>(v));
+        break;
+      }
+      default: break;
+    }
+    flags |= (p3_is_identity(R) ? 1u : 0u) | (okP ? 2u : 0u) | (okQ ? 4u : 0u);
+    p3_compress(ow, R);
+    f[0] = R.X; f[1] = R.Y; f[2] = R.Z; f[3] = R.T;
+  }
+  if (gid >= n) return;
+  uint32_t* o = out + 64 * (size_t)gid;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int i = 0; i < 9; i++) o[9 * k + i] = f[k].v[i];
+  o[36] = flags;
+  o[37] = o[38] = o[39] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) o[40 + i] = ow[i];
+#pragma unroll
+  for (int i = 0; i < 9; i++) o[48 + i] = extra.v[i];
+#pragma unroll
+  for (int i = 57; i < 64; i++) o[i] = 0;
+}
+
 // The number of invalid signatures (status MV_SIG_INVALID: the failures a combined equation
 // can see; s >= l and undecodable points are excluded from it exactly) of n statuses, added to
 // *count (zeroed by the launcher): the single-path feedback of the batch policy (engine.cpp
@@ -597,6 +845,11 @@ hipError_t launch_block_hash(const Knobs& kn, const uint8_t* buf, const uint64_t
 hipError_t launch_selftest(int op, const uint32_t* in, uint32_t n, const void* btab, uint32_t* out, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(mv::k_selftest, dim3((n + 63) / 64), dim3(64), 0, s, op, in, n, (const uint4*)btab, out);
+  return hipGetLastError();
+}
+hipError_t launch_selftest_wide(int op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(mv::k_selftest_wide, dim3((n + 63) / 64), dim3(64), 0, s, op, in, n, out);
   return hipGetLastError();
 }
 

@@ -33,8 +33,9 @@ MV_DEV fer sel(const fer& a0, const fer& a1, const fer& a2, const fer& a3) {
   return r;
 }
 
-// one parallel carry round at 29 bits: limbs < 2^32 in -> N out (lanes 1..8 < 2^29 + 8, lane 0
-// < 2^29 + 7 * 1216); limb 8's carry goes to limb 0 times 2^261 = 1216 (mod p)
+// one parallel carry round at 29 bits: limbs < 2^32 in -> N out (lanes 1..8 < 2^29 + 7, lane 0
+// <= 2^29 - 1 + 7 * 1216); limb 8's carry goes to limb 0 times 2^261 = 1216 (mod p). Every carry
+// is added to an already masked limb, so unlike fe_normalize's serial pass no 32-bit input wraps.
 MV_DEV fer carry(uint32_t x, const r16::Consts& K) {
   using namespace r16;
   const uint32_t k = x >> 29;

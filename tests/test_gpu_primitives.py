@@ -46,7 +46,9 @@ def test_fe_mul_sq_add_sub(engine):
 
 
 def test_fe_sub_tight_inputs(engine):
-    # fe_sub's contract: tight inputs (< 2^255 + 2^14) -- which every fe op returns
+    # fe25519.h: fe_sub takes N or A limbs for both operands; these are tight ones (values
+    # < 2^255 + 2^13 in limbs < 2^29). Lazy operands at the bounds: test_gpu_limb_bounds.py
+    # test_fe_sub_lazy_operands
     r = random.Random(2)
     items = [(a % (2**255 + 2**13), b % (2**255 + 2**13)) for a, b in pairs(r)]
     out = run(engine, 3, items)
