@@ -29,6 +29,12 @@
  *   mv_wal_layout          WalWriter::writev position arithmetic (wal.rs:150-188), host only
  *   mv_frame_blocks        the block byte strings of received NetworkMessage frames
  *                          (Network::handle_read_stream, network.rs:400-447), host only
+ *   mv_verify_frames       what a connection does with its received bytes, per message: the frame
+ *                          reads of handle_read_stream (network.rs:400-447), the decode of each
+ *                          NetworkMessage (network.rs:454-457, data.rs:83-96) and
+ *                          NetworkSyncer::process_blocks (net_sync.rs:314-383), whose first
+ *                          rejected block ends the message and the connection
+ *   mv_frame_messages      the same walk on the host for one stream, without the block verdicts
  *
  * Conventions
  *   - The caller owns every buffer passed in and out; they must stay valid for the call.
@@ -87,6 +93,15 @@ typedef int32_t mv_status;
 #define MV_WAL_CRC_MISMATCH 1     /* "Crc mismatch, expected .., found .." wal.rs:250-257 */
 #define MV_WAL_NONZERO_CRC_LEN0 2 /* "Non-zero crc at len 0" wal.rs:240-247 */
 #define MV_WAL_BAD_LENGTH 3       /* len < 16 or the entry runs past its map: Bytes::slice panics, wal.rs:249 */
+
+/* per-message verdicts of mv_verify_frames / mv_frame_messages: what the reference does with one
+ * received NetworkMessage (network.rs:400-457, net_sync.rs:272-383) */
+#define MV_MSG_OK 0                 /* decodes, and every block of it is MV_BLOCK_OK (also: no blocks) */
+#define MV_MSG_DECODE_ERROR 1       /* bincode::deserialize::<NetworkMessage> fails, network.rs:454-457 */
+#define MV_MSG_BLOCK_REJECTED 2     /* process_blocks returns Err at its first rejected block, net_sync.rs:352-361 */
+#define MV_MSG_TOO_MANY_REQUESTED 3 /* RequestBlocks above MAXIMUM_BLOCK_REQUEST = 50, net_sync.rs:30, 282-285 */
+#define MV_MSG_NOT_REACHED 4        /* after the message that ended the connection: never processed */
+#define MV_MSG_BAD_SIZE 5           /* frame size above MAX_SIZE = 16 MiB, network.rs:216, 419-422 */
 
 /* mv_config.flags */
 #define MV_FLAG_NO_BATCH 1u /* host-buffer verify: never use the batch (random linear combination) path */
@@ -216,6 +231,72 @@ uint64_t mv_wal_layout(const uint64_t* payload_len, uint64_t n, uint32_t map_bit
 int64_t mv_frame_blocks(const uint8_t* buf, uint64_t len, uint64_t* off, uint64_t* blen, uint64_t cap,
                         uint64_t* consumed);
 
+/* Received bytes verified per message (replaces, for many connections at once: the frame reads of
+ * Network::handle_read_stream, network.rs:400-447; bincode::deserialize::<NetworkMessage>,
+ * network.rs:454-457, which decodes every inner block, data.rs:83-96, before any is verified;
+ * and NetworkSyncer::process_blocks, net_sync.rs:314-383, which returns Err at the first
+ * rejected block, before add_blocks, and so ends the connection).
+ *
+ * Stream s is one connection's received bytes buf[soff[s], soff[s] + slen[s]); streams are only
+ * read and may overlap. A frame is a u32 big-endian size and that many bytes of
+ * bincode(NetworkMessage); size 0 is a ping with 8 more bytes (no message, no row). The walk of a
+ * stream stops before an incomplete trailing frame; consumed[s] = the bytes of the complete frames
+ * walked. Every other frame yields one message row of 8 uint32_t words, rows flat across streams
+ * in stream order, then arrival order:
+ *   [0] stream   [1] message tag   [2] [3] off: offset in buf of the frame's size word (low, high)
+ *   [4] first_block  [5] n_blocks: the message's blocks are blk_off / blk_len / blk_status
+ *       [first_block, first_block + n_blocks)
+ *   [6] status | bad_status << 8   [7] bad_block, or 0xFFFFFFFF
+ * status is MV_MSG_*:
+ *   OK                  the message decodes and all its blocks are MV_BLOCK_OK (messages without
+ *                       blocks and Blocks of count 0, net_sync.rs:320-322, included)
+ *   DECODE_ERROR        size < 4; tag > 4; tag 0 (Subscribe) with fewer than 8 body bytes; tags 1 / 3
+ *                       (Blocks, RequestBlocksResponse) whose count or a block length runs past the
+ *                       frame; tags 2 / 4 (RequestBlocks, BlockNotFound) with a BlockReference (u64,
+ *                       u64, u64 digest length, digest; types.rs:49-54, crypto.rs:322-347) that runs
+ *                       past the frame or whose digest length is not 32; or a block of a tag 1 / 3
+ *                       message is MV_BLOCK_PARSE_ERROR: bad_block = the first such block. This wins
+ *                       over an earlier rejected block of the message (the decode comes first).
+ *   BLOCK_REJECTED      every block parses; bad_block = the first one not MV_BLOCK_OK (its index in
+ *                       the message), bad_status = its MV_BLOCK_*
+ *   TOO_MANY_REQUESTED  a well-formed RequestBlocks of more than 50 references (BlockNotFound has
+ *                       no limit)
+ *   NOT_REACHED         the message follows the first message of its stream that is not OK
+ *   BAD_SIZE            size above 16 MiB
+ * The tag word is 0xFFFFFFFF where no tag was read (BAD_SIZE, and a DECODE_ERROR of size < 4).
+ * Trailing bytes after the message inside its frame are allowed (as mv_frame_blocks allows them).
+ * drop_msg[s] = the flat index of stream s's first row that is not OK, or 0xFFFFFFFF.
+ * The walk itself stops a stream at the first row the bytes alone condemn (BAD_SIZE: consumed
+ * ends before that frame; a frame-level DECODE_ERROR or TOO_MANY_REQUESTED: after it); a message
+ * whose count or length overruns lists no blocks (n_blocks 0). Messages after a row that turns
+ * bad only through a block verdict are still walked and their blocks verified; their rows
+ * then become NOT_REACHED.
+ * The reference skips blocks it has processed before (net_sync.rs:331-335) ahead of verify; such
+ * a block passed the same deterministic check then, so verifying it again changes no verdict.
+ *
+ * mv_frame_messages: host only, one stream buf[0, len), stream word 0. The rows carry the
+ * statuses the bytes alone decide (OK, frame-level DECODE_ERROR, TOO_MANY_REQUESTED, BAD_SIZE) and
+ * the walk stops after the first that is not OK; every listed block belongs to a row, and tags
+ * 0, 2 and 4 are bound-checked. Returns the number of rows (the first cap_msgs written, and the
+ * first cap_blocks blocks; *n_blocks = blocks found), or -1 for bad arguments. */
+int64_t mv_frame_messages(const uint8_t* buf, uint64_t len, uint32_t* msgs /* cap_msgs x 8 */, uint64_t cap_msgs,
+                          uint64_t* blk_off, uint64_t* blk_len, uint64_t cap_blocks, uint64_t* n_blocks,
+                          uint64_t* consumed);
+/* mv_verify_frames: ns streams of host buffer buf. On the device: the frame walk, the message
+ * walk, StatementBlock::verify of every listed block in place (the block path of
+ * mv_dev_verify_blocks: the comb kernels below MV_BATCH_MIN blocks per device, the walk / batch
+ * path from there), the message and stream verdicts. Requires mv_set_committee; takes the
+ * context in turn. Only the first cap_msgs rows and cap_blocks blocks are written; *n_msgs and
+ * *n_blocks are always the totals. blk_status (MV_BLOCK_*, optional) may be NULL. Several devices
+ * or logical shards: whole streams are split by bytes (mv_shard_plan weights slen + 64), and row
+ * and block indices are rebased, so the result does not depend on the split. Streams in
+ * page-locked memory (mv_host_alloc), in order and disjoint, are DMAd in place as
+ * mv_verify_blocks does; others are packed stream by stream first. */
+mv_status mv_verify_frames(mv_ctx* ctx, const uint8_t* buf, const uint64_t* soff, const uint64_t* slen, uint32_t ns,
+                           uint64_t* consumed /* ns */, uint32_t* drop_msg /* ns */, uint32_t* msgs /* cap_msgs x 8 */,
+                           uint64_t cap_msgs, uint64_t* n_msgs, uint64_t* blk_off, uint64_t* blk_len,
+                           uint8_t* blk_status /* may be NULL */, uint64_t cap_blocks, uint64_t* n_blocks);
+
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
  * library's stream for that device). They enqueue work and return without synchronising. */
@@ -255,6 +336,18 @@ mv_status mv_dev_verify_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, ui
 mv_status mv_dev_wal_verify(mv_ctx* ctx, int device, const uint8_t* d_wal, uint64_t size, uint64_t end_pos,
                             uint32_t map_bits, uint64_t* d_pos, uint32_t* d_tag, uint32_t* d_len, uint8_t* d_status,
                             uint64_t cap, uint64_t* count, void* stream);
+/* mv_verify_frames on received bytes already in HBM (handle_read_stream, the NetworkMessage decode
+ * and process_blocks as there: network.rs:400-457, net_sync.rs:314-383): d_buf, d_soff, d_slen
+ * and every output array are device memory; *n_msgs and *n_blocks are written on the host.
+ * Synchronises `stream` (the row and block counts depend on the data and size the lists). d_buf is
+ * 8-byte aligned and 16 bytes past buf_bytes are readable; a stream that reaches past buf_bytes
+ * is clipped to it. Streams whose blocks are verified must not overlap one another (the block
+ * path stages a block at its own offset, as mv_dev_verify_blocks). */
+mv_status mv_dev_verify_frames(mv_ctx* ctx, int device, const uint8_t* d_buf, uint64_t buf_bytes,
+                               const uint64_t* d_soff, const uint64_t* d_slen, uint32_t ns, uint64_t* d_consumed,
+                               uint32_t* d_drop_msg, uint32_t* d_msgs, uint64_t cap_msgs, uint64_t* n_msgs,
+                               uint64_t* d_blk_off, uint64_t* d_blk_len, uint8_t* d_blk_status, uint64_t cap_blocks,
+                               uint64_t* n_blocks, void* stream);
 /* crc32fast::hash of n strings of device buffer d_buf at d_off/d_len (device arrays) -> d_out. Enqueue only. */
 mv_status mv_dev_crc32(mv_ctx* ctx, int device, const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len,
                        uint32_t n, uint32_t* d_out, void* stream);

@@ -16,6 +16,12 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.wal_iter_until    the same as the reference's iterator: (pos, (tag, bytes)), raising
                            where the reference panics
   wal_layout               WalWriter::writev positions (wal.rs:150-188)
+  Engine.verify_frames_messages
+                           what a connection does with its received bytes, per message:
+                           handle_read_stream + the NetworkMessage decode (network.rs:400-457) and
+                           process_blocks (net_sync.rs:314-383), for many connections at once
+  Engine.dev_verify_frames the same on bytes already in HBM
+  frame_messages           the frame and message walk alone, on the host, for one stream
   crypto.*                 thin reference-named wrappers (BlockDigest, PublicKey, Signer, ...)
 """
 from __future__ import annotations
@@ -48,10 +54,14 @@ EXPORTS = [
     "mv_dev_ed25519_sign", "mv_selftest", "mv_block_preimage", "mv_dev_ed25519_verify_batch", "mv_batch_stats",
     "mv_set_stage_timing", "mv_stage_times", "mv_dev_verify_blocks", "mv_batch_counters", "mv_batch_routes", "mv_set_batch_groups",
     "mv_queue_stats", "mv_shard_plan", "mv_crc32", "mv_wal_verify", "mv_wal_layout", "mv_dev_wal_verify",
-    "mv_frame_blocks",
+    "mv_frame_blocks", "mv_frame_messages", "mv_verify_frames", "mv_dev_verify_frames",
     "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
+# per-message verdicts (mv_verify_frames rows, word 6's low byte) and the rows' "none" word
+MSG_STATUS = ["OK", "DECODE_ERROR", "BLOCK_REJECTED", "TOO_MANY_REQUESTED", "NOT_REACHED", "BAD_SIZE"]
+MSG_OK, MSG_DECODE_ERROR, MSG_BLOCK_REJECTED, MSG_TOO_MANY_REQUESTED, MSG_NOT_REACHED, MSG_BAD_SIZE = range(6)
+MSG_NONE = 0xFFFFFFFF
 WAL_MAP_BITS, WAL_MAP_BITS_TEST = 24, 16  # wal.rs:95-103
 # batch path stages, the block pipeline's, the WAL replay's (mv_stage_times order, MV_NSTAGES)
 STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "hash", "verify", "verdict", "wal_walk",
@@ -115,6 +125,11 @@ def load_library(path: str = LIB_PATH):
     lib.mv_wal_layout.restype = u64
     lib.mv_frame_blocks.argtypes = [vp, u64, vp, vp, u64, vp]
     lib.mv_frame_blocks.restype = ctypes.c_int64
+    lib.mv_frame_messages.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp]
+    lib.mv_frame_messages.restype = ctypes.c_int64
+    lib.mv_verify_frames.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp]
+    lib.mv_dev_verify_frames.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64,
+                                         vp, vp]
     lib.mv_dev_wal_verify.argtypes = [vp, ctypes.c_int, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp]
     lib.mv_dev_crc32.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, vp, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
@@ -297,7 +312,60 @@ class Engine:
         st, md, bd = self.verify_blocks_packed(buf, offs, lens)
         return st, md, bd, consumed
 
+    def verify_frames_messages(self, buf, soff, slen) -> "FrameVerdicts":
+        """The received bytes of many connections verified per message (mv_verify_frames:
+        handle_read_stream, the NetworkMessage decode and process_blocks, network.rs:400-457,
+        net_sync.rs:314-383). Stream s is buf[soff[s], soff[s] + slen[s]). Returns a FrameVerdicts:
+        one row per message (n x 8 uint32), consumed bytes and the first dropped row per stream,
+        and the listed blocks with their MV_BLOCK_* statuses."""
+        buf = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray)) else buf,
+                                   dtype=np.uint8)
+        soff = np.ascontiguousarray(np.asarray(soff, dtype=np.uint64))
+        slen = np.ascontiguousarray(np.asarray(slen, dtype=np.uint64))
+        ns = soff.shape[0]
+        if ns and int((soff + slen).max()) > buf.size:
+            raise ValueError("a stream reaches past the buffer")
+        consumed = np.zeros(max(ns, 1), dtype=np.uint64)
+        drop = np.zeros(max(ns, 1), dtype=np.uint32)
+        nm, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        pb = _p(buf) if buf.size else _p(np.zeros(1, dtype=np.uint8))
+        # a frame takes at least 5 bytes and a block at least its 8-byte length; large inputs start
+        # from a guess below that bound, and a call whose totals exceed it is repeated at the totals
+        total = int(slen.sum()) if ns else 0
+        cap_m = min(total // 5 + 1, max(1 << 16, total // 256))
+        cap_b = min(total // 8 + 1, max(1 << 16, total // 128))
+        while True:
+            rows = np.zeros((cap_m, 8), dtype=np.uint32)
+            off = np.zeros(cap_b, dtype=np.uint64)
+            ln = np.zeros(cap_b, dtype=np.uint64)
+            st = np.zeros(cap_b, dtype=np.uint8)
+            self._check(self.lib.mv_verify_frames(self.ctx, pb, _p(soff), _p(slen), ns, _p(consumed), _p(drop),
+                                                  _p(rows), cap_m, ctypes.byref(nm), _p(off), _p(ln), _p(st), cap_b,
+                                                  ctypes.byref(nb)), "mv_verify_frames")
+            n, b = int(nm.value), int(nb.value)
+            if n <= cap_m and b <= cap_b:
+                break
+            cap_m, cap_b = max(cap_m, n), max(cap_b, b)
+        return FrameVerdicts(rows[:n].copy(), consumed[:ns].copy(), drop[:ns].copy(), off[:b].copy(), ln[:b].copy(),
+                             st[:b].copy())
+
     # ---- device-resident (torch tensors on the device) ----
+    def dev_verify_frames(self, device: int, d_buf, buf_bytes: int, d_soff, d_slen, d_consumed, d_drop_msg, d_msgs,
+                          d_blk_off, d_blk_len, d_blk_status=None, stream_handle: int = 0) -> Tuple[int, int]:
+        """mv_dev_verify_frames on torch device tensors (d_buf uint8, 8-byte aligned with 16 readable
+        bytes past buf_bytes; d_soff / d_slen / d_consumed / d_blk_off / d_blk_len int64; d_drop_msg
+        and d_msgs (cap x 8) int32; d_blk_status uint8). Synchronises the stream; returns the
+        (message, block) totals, of which the first d_msgs.shape[0] / d_blk_off.shape[0] are written."""
+        vp = ctypes.c_void_p
+        nm, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.lib.mv_dev_verify_frames(
+            self.ctx, device, vp(d_buf.data_ptr()), int(buf_bytes), vp(d_soff.data_ptr()), vp(d_slen.data_ptr()),
+            d_soff.shape[0], vp(d_consumed.data_ptr()), vp(d_drop_msg.data_ptr()), vp(d_msgs.data_ptr()),
+            d_msgs.shape[0], ctypes.byref(nm), vp(d_blk_off.data_ptr()), vp(d_blk_len.data_ptr()),
+            vp(d_blk_status.data_ptr()) if d_blk_status is not None else None, d_blk_off.shape[0], ctypes.byref(nb),
+            vp(stream_handle or None)), "mv_dev_verify_frames")
+        return int(nm.value), int(nb.value)
+
     def dev_verify(self, device: int, d_msg, d_sig, d_pk, d_status, stream_handle: int = 0):
         n = d_msg.shape[0]
         self._check(self.lib.mv_dev_ed25519_verify(self.ctx, device, ctypes.c_void_p(d_msg.data_ptr()),
@@ -519,6 +587,50 @@ def frame_blocks(buf) -> Tuple[np.ndarray, np.ndarray, int]:
     lens = np.zeros(max(n, 1), dtype=np.uint64)
     lib.mv_frame_blocks(_p(b) if b.size else None, b.size, _p(offs), _p(lens), n, ctypes.byref(consumed))
     return offs[:n], lens[:n], int(consumed.value)
+
+
+class FrameVerdicts:
+    """Result of Engine.verify_frames_messages / frame_messages. rows: (n, 8) uint32 message rows
+    (include/mysti_verify.h: stream, tag, off low / high, first_block, n_blocks,
+    status | bad_status << 8, bad_block); consumed and drop_msg per stream; blk_off / blk_len /
+    blk_status per listed block (blk_status is None for the host-only walk)."""
+
+    def __init__(self, rows, consumed, drop_msg, blk_off, blk_len, blk_status):
+        self.rows, self.consumed, self.drop_msg = rows, consumed, drop_msg
+        self.blk_off, self.blk_len, self.blk_status = blk_off, blk_len, blk_status
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.rows[:, 6] & 0xFF
+
+    @property
+    def bad_status(self) -> np.ndarray:
+        return (self.rows[:, 6] >> 8) & 0xFF
+
+    @property
+    def off(self) -> np.ndarray:
+        return self.rows[:, 2].astype(np.uint64) | (self.rows[:, 3].astype(np.uint64) << np.uint64(32))
+
+
+def frame_messages(buf) -> FrameVerdicts:
+    """Host-only: the message rows of one stream of received frames (mv_frame_messages: the walk
+    of mv_verify_frames with the statuses the bytes alone decide) and the blocks they list."""
+    lib = load_library()
+    b = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray)) else buf,
+                             dtype=np.uint8)
+    pb = _p(b) if b.size else None
+    consumed, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    n = lib.mv_frame_messages(pb, b.size, None, 0, None, None, 0, ctypes.byref(nb), ctypes.byref(consumed))
+    if n < 0:
+        raise MvError("mv_frame_messages: bad arguments")
+    rows = np.zeros((max(n, 1), 8), dtype=np.uint32)
+    offs = np.zeros(max(nb.value, 1), dtype=np.uint64)
+    lens = np.zeros(max(nb.value, 1), dtype=np.uint64)
+    lib.mv_frame_messages(pb, b.size, _p(rows), n, _p(offs), _p(lens), nb.value, ctypes.byref(nb),
+                          ctypes.byref(consumed))
+    drop = np.array([next((i for i in range(n) if rows[i, 6] & 0xFF), MSG_NONE)], dtype=np.uint32)
+    return FrameVerdicts(rows[:n], np.array([consumed.value], dtype=np.uint64), drop, offs[:nb.value],
+                         lens[:nb.value], None)
 
 
 def version() -> str:

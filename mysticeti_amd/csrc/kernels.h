@@ -318,4 +318,45 @@ hipError_t launch_wal_compact(const unsigned long long* rec, uint32_t cap_pm, co
 hipError_t launch_wal_crc(const uint8_t* img, uint64_t size, const unsigned long long* ent, uint64_t total,
                           const uint32_t* tables, uint64_t* out_pos, uint32_t* out_tag, uint32_t* out_len,
                           uint8_t* out_status, uint64_t cap, unsigned long long* first_fail, int cus, hipStream_t s);
+// frames.hip: the walk of received NetworkMessage frames and the per-message / per-connection
+// verdicts of mv_verify_frames (rules: frame_walk.h). Stream s = buf[soff[s], soff[s] + slen[s])
+// clipped to buf_bytes. Count / scan / list as the WAL walk: the first launch_frame_walk
+// (foff == nullptr) writes fcount[s] (frames that get a row) and consumed[s]; the second lists
+// stream s's frames at foff[s] (offset of the size word, size, stream).
+hipError_t launch_frame_walk(const uint8_t* buf, uint64_t buf_bytes, const uint64_t* soff, const uint64_t* slen,
+                             uint32_t ns, const uint64_t* foff, uint64_t* fr_off, uint32_t* fr_size,
+                             uint32_t* fr_stream, uint32_t* fcount, uint64_t* consumed, hipStream_t s);
+struct FrameList {  // nf frames: the walk's list, and per frame the message's tag, status, blocks
+  const uint64_t* off;
+  const uint32_t* size;
+  const uint32_t* stream;
+  uint64_t nf;
+  uint32_t* tag;
+  uint8_t* status;  // MV_MSG_OK / DECODE_ERROR / TOO_MANY_REQUESTED / BAD_SIZE
+  uint32_t* nblk;
+};
+struct FrameRows {  // the second message walk's inputs (per stream / per frame) and outputs
+  const uint64_t* foff;       // per stream: its first frame
+  const uint32_t* kept;       // per stream: rows kept (launch_stream_cut)
+  const uint32_t* row_base;   // per stream: its first row
+  const uint32_t* blk_base;   // per stream: its first block
+  const uint64_t* bpre;       // per frame: blocks of the stream's earlier frames
+  uint32_t* rows;             // n_rows x 8 words (include/mysti_verify.h)
+  uint64_t n_rows;
+  uint64_t* blk_off;          // n_blk
+  uint64_t* blk_len;
+  uint64_t n_blk;
+};
+// one lane per frame; out == nullptr: tag / status / nblk of every frame, else rows + block lists
+hipError_t launch_msg_walk(const uint8_t* buf, const FrameList& fl, const FrameRows* out, hipStream_t s);
+// one lane per stream: kept[s] (rows up to and including the first the bytes alone condemn),
+// sblocks[s] (their blocks), bpre per frame; consumed[s] ends after a frame-level decode error
+hipError_t launch_stream_cut(const uint64_t* soff, uint64_t buf_bytes, uint32_t ns, const uint32_t* fcount,
+                             const uint64_t* foff, const FrameList& fl, uint64_t* bpre, uint32_t* kept,
+                             uint64_t* sblocks, uint64_t* consumed, hipStream_t s);
+// k_msg_verdict (block statuses -> row status, bad_block, bad_status) then k_stream_verdict
+// (drop_msg[s], later rows MV_MSG_NOT_REACHED)
+hipError_t launch_frame_verdicts(uint32_t* rows, uint64_t n_rows, const uint8_t* blk_status, uint64_t n_blk,
+                                 uint32_t ns, const uint32_t* kept, const uint32_t* row_base, uint32_t* drop_msg,
+                                 hipStream_t s);
 }  // namespace mvk

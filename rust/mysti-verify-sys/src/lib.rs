@@ -47,6 +47,13 @@ pub const MV_WAL_CRC_MISMATCH: u8 = 1;
 pub const MV_WAL_NONZERO_CRC_LEN0: u8 = 2;
 pub const MV_WAL_BAD_LENGTH: u8 = 3;
 
+pub const MV_MSG_OK: u32 = 0;
+pub const MV_MSG_DECODE_ERROR: u32 = 1;
+pub const MV_MSG_BLOCK_REJECTED: u32 = 2;
+pub const MV_MSG_TOO_MANY_REQUESTED: u32 = 3;
+pub const MV_MSG_NOT_REACHED: u32 = 4;
+pub const MV_MSG_BAD_SIZE: u32 = 5;
+
 pub const MV_FLAG_NO_BATCH: u32 = 1;
 pub const MV_FLAG_NO_COMB: u32 = 2;
 pub const MV_FLAG_HOST_PARSE: u32 = 4;
@@ -83,6 +90,18 @@ extern "C" {
     pub fn mv_wal_layout(payload_len: *const u64, n: u64, map_bits: u32, start: u64, pos: *mut u64) -> u64;
     pub fn mv_frame_blocks(buf: *const u8, len: u64, off: *mut u64, blen: *mut u64, cap: u64,
                            consumed: *mut u64) -> i64;
+    pub fn mv_frame_messages(buf: *const u8, len: u64, msgs: *mut u32, cap_msgs: u64, blk_off: *mut u64,
+                             blk_len: *mut u64, cap_blocks: u64, n_blocks: *mut u64,
+                             consumed: *mut u64) -> i64;
+    pub fn mv_verify_frames(ctx: *mut mv_ctx, buf: *const u8, soff: *const u64, slen: *const u64, ns: u32,
+                            consumed: *mut u64, drop_msg: *mut u32, msgs: *mut u32, cap_msgs: u64,
+                            n_msgs: *mut u64, blk_off: *mut u64, blk_len: *mut u64, blk_status: *mut u8,
+                            cap_blocks: u64, n_blocks: *mut u64) -> i32;
+    pub fn mv_dev_verify_frames(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,
+                                d_soff: *const u64, d_slen: *const u64, ns: u32, d_consumed: *mut u64,
+                                d_drop_msg: *mut u32, d_msgs: *mut u32, cap_msgs: u64, n_msgs: *mut u64,
+                                d_blk_off: *mut u64, d_blk_len: *mut u64, d_blk_status: *mut u8,
+                                cap_blocks: u64, n_blocks: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_dev_ed25519_verify(ctx: *mut mv_ctx, device: i32, d_msg: *const u8, d_sig: *const u8,
                                  d_pk: *const u8, n: u32, d_status: *mut u8, stream: *mut c_void) -> i32;
     pub fn mv_dev_ed25519_verify_batch(ctx: *mut mv_ctx, device: i32, d_msg: *const u8, d_sig: *const u8,

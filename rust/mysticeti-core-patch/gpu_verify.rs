@@ -83,12 +83,75 @@ impl GpuVerifier {
             .map(|((b, s), d)| verdict_to_result(b, s, d, committee))
             .collect()
     }
+
+    /// What the reference does with the received bytes of many connections, per message
+    /// (handle_read_stream + the NetworkMessage decode, network.rs:400-457; process_blocks,
+    /// net_sync.rs:314-383): `streams[s]` = (offset, length) of connection s's bytes in `buf`.
+    /// One mv_verify_frames call walks the frames, verifies the blocks in place and returns the
+    /// message rows (8 words each, include/mysti_verify.h), per connection the consumed bytes and
+    /// the first row that is not MV_MSG_OK (u32::MAX: keep the connection), and the listed blocks.
+    pub fn verify_frames(&self, buf: &[u8], streams: &[(u64, u64)]) -> eyre::Result<FrameVerdicts> {
+        let soff: Vec<u64> = streams.iter().map(|s| s.0).collect();
+        let slen: Vec<u64> = streams.iter().map(|s| s.1).collect();
+        ensure!(streams.iter().all(|s| s.0 <= buf.len() as u64 && s.1 <= buf.len() as u64 - s.0), "stream out of buf");
+        let ns = streams.len();
+        let mut out = FrameVerdicts { consumed: vec![0; ns], drop_msg: vec![0; ns], ..Default::default() };
+        let (mut cap_m, mut cap_b) = (1024usize, 4096usize);
+        loop {
+            out.rows.resize(8 * cap_m, 0);
+            out.blk_off.resize(cap_b, 0);
+            out.blk_len.resize(cap_b, 0);
+            out.blk_status.resize(cap_b, 0);
+            let (mut n_msgs, mut n_blocks) = (0u64, 0u64);
+            let rc = unsafe {
+                sys::mv_verify_frames(self.ctx, buf.as_ptr(), soff.as_ptr(), slen.as_ptr(), ns as u32,
+                                      out.consumed.as_mut_ptr(), out.drop_msg.as_mut_ptr(), out.rows.as_mut_ptr(),
+                                      cap_m as u64, &mut n_msgs, out.blk_off.as_mut_ptr(), out.blk_len.as_mut_ptr(),
+                                      out.blk_status.as_mut_ptr(), cap_b as u64, &mut n_blocks)
+            };
+            ensure!(rc == sys::MV_OK, "mv_verify_frames: {}", self.last_error());
+            let (m, b) = (n_msgs as usize, n_blocks as usize);
+            if m <= cap_m && b <= cap_b {
+                out.rows.truncate(8 * m);
+                out.blk_off.truncate(b);
+                out.blk_len.truncate(b);
+                out.blk_status.truncate(b);
+                return Ok(out);
+            }
+            // the totals always come back: once more with room for all of them
+            cap_m = cap_m.max(m);
+            cap_b = cap_b.max(b);
+        }
+    }
 }
 
-/// The blocks of received network frames (network.rs:400-447: u32 BE size + bincode
-/// NetworkMessage) as (offsets, lengths) into `buf`, and the bytes of the complete frames: a
-/// receiver that reads frames into one buffer passes it and these arrays to mv_verify_blocks
-/// without deserializing. An error where Network::handle_read_stream drops the connection.
+/// Result of `GpuVerifier::verify_frames` (layout: include/mysti_verify.h, mv_verify_frames).
+#[derive(Default)]
+pub struct FrameVerdicts {
+    pub rows: Vec<u32>,      // 8 words per message
+    pub consumed: Vec<u64>,  // per connection
+    pub drop_msg: Vec<u32>,  // per connection: first row not MV_MSG_OK, or u32::MAX
+    pub blk_off: Vec<u64>,
+    pub blk_len: Vec<u64>,
+    pub blk_status: Vec<u8>, // MV_BLOCK_*
+}
+
+impl FrameVerdicts {
+    /// MV_MSG_* of row r.
+    pub fn status(&self, r: usize) -> u32 {
+        self.rows[8 * r + 6] & 0xff
+    }
+}
+
+/// The blocks of one stream of received network frames (network.rs:400-447: u32 BE size + bincode
+/// NetworkMessage) as a flat list of (offsets, lengths) into `buf`, and the bytes of the complete
+/// frames, for mv_verify_blocks on the same buffer. This is NOT what the reference does with a
+/// connection: the list carries no message index (so "the first rejected block ends its message",
+/// net_sync.rs:352-361, has to be rebuilt by the caller), an unparsable block's siblings are still
+/// listed although the reference fails the whole message (data.rs:83-96, network.rs:454-457), and
+/// Subscribe / RequestBlocks / BlockNotFound bodies are skipped unchecked. Use
+/// `GpuVerifier::verify_frames` (mv_verify_frames) for the reference's per-message behaviour. An
+/// error where a size, a tag or a block length makes handle_read_stream drop the connection.
 pub fn frame_blocks(buf: &[u8]) -> eyre::Result<(Vec<u64>, Vec<u64>, usize)> {
     let mut consumed = 0u64;
     let n = unsafe {
