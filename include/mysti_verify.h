@@ -129,7 +129,10 @@ const char* mv_last_error(const mv_ctx* ctx);
 const char* mv_version(void);
 
 /* Committee: n authority keys (32-byte encodings) and stakes, committee epoch.
- * key_ok[i] (optional) receives 1 if key i decodes (VerificationKey::try_from). */
+ * key_ok[i] (optional) receives 1 if key i decodes (VerificationKey::try_from).
+ * MV_E_INVALID_ARG (the committee in force stays) when n is 0 or above 512, or when the total
+ * stake or twice the total does not fit in 64 bits: Committee::new refuses an overflowing total
+ * (committee.rs:50-54), and the quorum threshold is 2 * total / 3 (committee.rs:56-57). */
 mv_status mv_set_committee(mv_ctx* ctx, const uint8_t* pks /* n x 32 */, const uint64_t* stakes, uint32_t n,
                            uint64_t epoch, uint8_t* key_ok /* n, may be NULL */);
 

@@ -2312,6 +2312,14 @@ const char* mv_last_error(const mv_ctx* ctx) { return ctx ? ctx->err.c_str() : "
 mv_status mv_set_committee(mv_ctx* ctx, const uint8_t* pks, const uint64_t* stakes, uint32_t n, uint64_t epoch,
                            uint8_t* key_ok) {
   if (!ctx || !pks || !stakes || n == 0 || n > 512) return set_err(ctx, MV_E_INVALID_ARG, "bad committee args");
+  // total = checked sum (committee.rs:50-54: "Total stake overflow"); 2 * total must fit as well,
+  // or the quorum threshold 2 * total / 3 would wrap and almost any parent set would pass it
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++)
+    if (__builtin_add_overflow(total, stakes[i], &total))
+      return set_err(ctx, MV_E_INVALID_ARG, "committee stakes: the total stake does not fit in 64 bits");
+  if (total > UINT64_MAX / 2)
+    return set_err(ctx, MV_E_INVALID_ARG, "committee stakes: twice the total stake does not fit in 64 bits");
   std::unique_lock<std::shared_mutex> cl(ctx->com_mu);  // no online request in flight
   std::lock_guard<std::mutex> lk(ctx->mu);
   for (auto& dev : ctx->devs)
@@ -2325,8 +2333,6 @@ mv_status mv_set_committee(mv_ctx* ctx, const uint8_t* pks, const uint64_t* stak
   c.pks.assign(pks, pks + 32 * (size_t)n);
   c.stakes.assign(stakes, stakes + n);
   c.epoch = epoch;
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n; i++) total += stakes[i];
   c.quorum_threshold = 2 * total / 3;
   // unpublish first: if a device step fails below, the context is left with no committee
   // (block calls then refuse with MV_E_NO_COMMITTEE) rather than host facts that disagree
