@@ -394,7 +394,9 @@ mv_status mv_stage_times(mv_ctx* ctx, double* ms /* MV_NSTAGES or NULL */, uint6
  * afterwards, between calls (no call on ctx in flight); name is the environment name and value
  * an integer (0 / 1 for on/off switches). Unknown names, and the switches consumed by
  * mv_create (MV_PASS_SETS, MV_GUARD_GROUPS, MV_BASE_GROUPS), are MV_E_INVALID_ARG. No switch
- * changes a verdict, digest or crc. */
+ * changes a verdict, digest or crc. mv_get_option also reads "MV_LIVE_RESOURCES", the
+ * process-wide count of live device resources (buffers, events, streams, retired blocks);
+ * mv_set_option refuses it. */
 mv_status mv_set_option(mv_ctx* ctx, const char* name, int64_t value);
 mv_status mv_get_option(mv_ctx* ctx, const char* name, int64_t* value);
 /* Runs field/scalar primitive `op` on n lane inputs (16 words each) -> 16 words each (host buffers).

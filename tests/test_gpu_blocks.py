@@ -248,7 +248,7 @@ def test_pinned_caller_buffer_is_read_in_place(engine):
 
 def test_batch_call_in_two_halves_matches_small_calls(engine):
     """8,300 config-4-shaped blocks in one call (both halves >= MV_BATCH_MIN: the parse of the second
-    half runs on another stream beside the hash of the first, engine.cpp enqueue_blocks), with
+    half runs on another stream beside the hash of the first, engine_blocks.cpp enqueue_blocks), with
     tampered and truncated blocks in both halves: every verdict and digest equals the one the
     same block gets in 64-block calls (the comb path, held to the oracle by the tests above)."""
     import mysticeti_amd.blocks as MB

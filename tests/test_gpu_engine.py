@@ -485,3 +485,76 @@ def test_online_service_one_block_callers(engine, golden, opts, kmax):
     est, _, _ = _concurrent(engine, ebins, threads=8, rounds=1, kmax=2)
     assert (est == want).all(), np.nonzero(est != want)[0][:8]
     engine.set_committee(pks, stakes, 0)
+
+
+def _use_every_allocating_route(eng, golden):
+    """Makes `eng` allocate along every route that holds device resources until mv_destroy: the
+    committee tables, the host-buffer batch path, the dense-failure single route (its rejected
+    counts), the pinned signature pipeline (staging slots and their events), and a block call
+    through the resident service and one through the submission queue."""
+    g = golden("blocks_config1.json")
+    pks = np.frombuffer(b"".join(bytes.fromhex(x) for x in g["committee"]["pks"]), dtype=np.uint8).reshape(-1, 32)
+    assert pks.shape[0] == 4
+    eng.set_committee(pks, np.array(g["committee"]["stakes"], dtype=np.uint64), g["committee"]["epoch"])
+    k = golden("sig_kat.json")[0]
+    row = lambda h, n: np.tile(np.frombuffer(bytes.fromhex(h), dtype=np.uint8), (n, 1))
+    n = M.BATCH_MIN
+    msg, sig, pk = row(k["msg"], n), row(k["sig"], n), row(k["pk"], n)
+    assert (eng.ed25519_verify(msg, sig, pk) == 0).all()  # one batch equation
+    # dense failures, at the smallest batch: 4 chunks of 1,024, a bad signature in each
+    bad = np.arange(5, n, 1024)
+    s_bad = sig.copy()
+    s_bad[bad, 40] ^= 0x10
+    want = np.zeros(n, np.uint8)
+    want[bad] = 1
+    r0 = eng.batch_routes()
+    for _ in range(3):  # one equation fails; 4 guarded groups all fail (dense); the single route
+        assert (eng.ed25519_verify(msg, s_bad, pk) == want).all()
+    r1 = eng.batch_routes()
+    assert (r1[0] - r0[0], r1[1] - r0[1], r1[2] - r0[2]) == (2, 1, 1)
+    eng.set_batch_groups(0)
+    # pinned inputs just over 8 x MV_BATCH_MIN: the streamed pipeline
+    n = 8 * M.BATCH_MIN + 1
+    hm, hs, hp = eng.host_empty((n, 32)), eng.host_empty((n, 64)), eng.host_empty((n, 32))
+    hm[:], hs[:], hp[:] = row(k["msg"], n), row(k["sig"], n), row(k["pk"], n)
+    live0 = eng.get_option("MV_LIVE_RESOURCES")
+    assert (eng.ed25519_verify(hm, hs, hp) == 0).all()
+    # the streamed pipeline ran: it alone makes 64 per-chunk events for each of its 3 input
+    # buffer sets (then the staging slot and its two events, which mv_destroy used to forget)
+    assert eng.get_option("MV_LIVE_RESOURCES") - live0 >= 3 * 64 + 3
+    for a in (hm, hs, hp):
+        eng.host_free(a)
+    blocks = [bytes.fromhex(x["bincode"]) for x in g["first"][:2]]
+    o0, q0 = eng.online_stats()[0], eng.queue_stats()[0]
+    assert (eng.verify_blocks(blocks)[0] == 0).all()
+    with eng.option("MV_ONLINE", 0):
+        assert (eng.verify_blocks(blocks)[0] == 0).all()
+    assert eng.online_stats()[0] == o0 + 1 and eng.queue_stats()[0] == q0 + 1
+
+
+def test_destroyed_context_leaves_no_live_resources(golden):
+    """mv_destroy releases everything a context held: the process-wide count of live buffers,
+    events, streams and retired blocks (MV_LIVE_RESOURCES) is back at what a fresh context holds
+    after a second context has allocated along every route and been destroyed, three times over
+    (the rejected counts of the dense-failure route and the pinned signature path's staging
+    and events used to be left behind)."""
+    g = golden("blocks_config1.json")
+    pks = np.frombuffer(b"".join(bytes.fromhex(x) for x in g["committee"]["pks"]), dtype=np.uint8).reshape(-1, 32)
+    with M.Engine(devices=(0,)) as first:
+        # (a committee change frees the device's retired blocks, whichever context retired them,
+        # as mv_destroy does: the base is read with none pending)
+        first.set_committee(pks, np.array(g["committee"]["stakes"], dtype=np.uint64), g["committee"]["epoch"])
+        base = first.get_option("MV_LIVE_RESOURCES")
+        assert base > 0
+        for _ in range(3):
+            with M.Engine(devices=(0,)) as eng:
+                _use_every_allocating_route(eng, golden)
+                assert first.get_option("MV_LIVE_RESOURCES") > base
+            assert first.get_option("MV_LIVE_RESOURCES") == base
+
+
+def test_live_resources_is_read_only(engine):
+    v = engine.get_option("MV_LIVE_RESOURCES")
+    with pytest.raises(M.MvError, match=r"failed \(-1\).*read-only"):  # MV_E_INVALID_ARG
+        engine.set_option("MV_LIVE_RESOURCES", 0)
+    assert engine.get_option("MV_LIVE_RESOURCES") == v
