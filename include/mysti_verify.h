@@ -26,6 +26,12 @@
  *   mv_wal_verify          WalReader::iter_until + WalIterator::next over WalReader::try_read
  *                          (wal.rs:226-346): the entry walk and crc check of the WAL replay in
  *                          BlockStore::open (block_store.rs:66)
+ *   mv_wal_replay          the replay loop of BlockStore::open on top of that walk (block_store.rs:50-116):
+ *                          the tag match (:71-99), the decode of WAL_ENTRY_BLOCK / WAL_ENTRY_OWN_BLOCK
+ *                          entries (:73-74, 83-84, 526-540), each block's BlockReference for add_unloaded,
+ *                          highest_round and last_seen_by_authority (:398-404, 424-432), and the positions
+ *                          RecoveredStateBuilder wants (state.rs:39-59); also StatementBlock::verify of
+ *                          every block, which the reference's replay skips
  *   mv_wal_layout          WalWriter::writev position arithmetic (wal.rs:150-188), host only
  *   mv_frame_blocks        the block byte strings of received NetworkMessage frames
  *                          (Network::handle_read_stream, network.rs:400-447), host only
@@ -93,6 +99,13 @@ typedef int32_t mv_status;
 #define MV_WAL_CRC_MISMATCH 1     /* "Crc mismatch, expected .., found .." wal.rs:250-257 */
 #define MV_WAL_NONZERO_CRC_LEN0 2 /* "Non-zero crc at len 0" wal.rs:240-247 */
 #define MV_WAL_BAD_LENGTH 3       /* len < 16 or the entry runs past its map: Bytes::slice panics, wal.rs:249 */
+/* ... and of the replay loop of BlockStore::open, produced by mv_wal_replay / mv_dev_wal_replay only
+ * (each is a panic of the reference) */
+#define MV_WAL_UNKNOWN_TAG 4       /* tag not in 1..5: "Unknown wal tag", block_store.rs:98 */
+#define MV_WAL_BLOCK_DECODE 5      /* tag 1 whose payload does not deserialize (block_store.rs:73-74); tag 3 with */
+                                   /* fewer than 8 payload bytes (:531) or whose block, from byte 8 on, does not (:84, 534) */
+#define MV_WAL_UNKNOWN_AUTHORITY 6 /* the block decodes, its authority >= the committee size: the expect in */
+                                   /* update_last_seen_by_authority, block_store.rs:424-428 */
 
 /* per-message verdicts of mv_verify_frames / mv_frame_messages: what the reference does with one
  * received NetworkMessage (network.rs:400-457, net_sync.rs:272-383) */
@@ -213,6 +226,46 @@ mv_status mv_crc32(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off, const u
 mv_status mv_wal_verify(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
                         uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap,
                         uint64_t* count);
+
+/* WAL replay up to the block-store index: what BlockStore::open does with a WAL (block_store.rs:50-116),
+ * with the blocks verified. The walk and the crc check are mv_wal_verify's (same arguments, same
+ * pos / tag / len / status / count, same iteration order, the first `cap` entries written); the
+ * image stays in device memory and the rest of the replay loop runs on it there:
+ *
+ * Entries. Where mv_wal_verify says MV_WAL_OK, the replay loop's own panics become the entry's
+ * status: MV_WAL_UNKNOWN_TAG (tag not in 1..5), MV_WAL_BLOCK_DECODE (a tag-1 payload, or a tag-3
+ * payload from byte 8 on, that is MV_BLOCK_PARSE_ERROR; a tag-3 payload under 8 bytes; also a
+ * tag-1 / tag-3 payload that reaches past `size`, whose zero tail the library does not read),
+ * MV_WAL_UNKNOWN_AUTHORITY (the block decodes but its authority >= the committee size; the decode
+ * is checked first). The list ends with the first entry, in iteration order, whose status is not
+ * MV_WAL_OK, whatever made it so; *count includes that entry.
+ * The payloads of tags 2, 4 and 5 (payload, state, commit) are not decoded: RecoveredStateBuilder
+ * decodes them on the host (state.rs:39-59), from pos / len.
+ *
+ * Block rows. One row of 10 uint64_t words per tag-1 / tag-3 entry that is MV_WAL_OK after all of
+ * the above, in iteration order (the failing entry and everything after it get none):
+ *   [0] entry index   [1] offset of the block's bincode in the image (pos + 16, + 8 for tag 3)
+ *   [2] its length    [3] authority   [4] round
+ *   [5..8] the 32 digest bytes as stored (four little-endian words): the claimed digest, the index
+ *          key of add_unloaded
+ *   [9] OwnBlockData::next_entry of a tag-3 entry (the payload's first u64), else UINT64_MAX
+ * blk_status[r] (optional) = the MV_BLOCK_* of StatementBlock::verify on row r's block. A block
+ * that parses but is rejected (digest mismatch, bad signature, threshold clock, ...) does not end
+ * the replay -- the reference does not verify here -- the status is information for the caller.
+ * *n_blocks = the number of rows; the first cap_blocks are written.
+ *
+ * Summary, over the rows kept: summary[0] = highest_round (0 without rows); summary[1] = the row
+ * index of the last tag-3 row, or UINT64_MAX (last_own_block, state.rs:49-54); summary[2] = the entry
+ * index of the last MV_WAL_OK tag-4 entry, or UINT64_MAX (it clears unprocessed_blocks, state.rs:56-59);
+ * last_seen[a] (committee size words) = the largest round of authority a's rows, 0 if none
+ * (block_store.rs:57, 424-432).
+ * Requires mv_set_committee (MV_E_NO_COMMITTEE otherwise), as BlockStore::open takes the committee.
+ * One image runs on one device (the context's first), as mv_wal_verify; takes the context in turn. */
+mv_status mv_wal_replay(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
+                        uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap, uint64_t* count,
+                        uint64_t* blk_rows /* cap_blocks x 10 */, uint8_t* blk_status /* cap_blocks, may be NULL */,
+                        uint64_t cap_blocks, uint64_t* n_blocks, uint64_t* summary /* 3 */,
+                        uint64_t* last_seen /* committee size */);
 
 /* Host-only helper: WalWriter::writev positions of n entries of payload_len[i] bytes written from
  * writer position `start` (an entry that would straddle a map starts at the next one); returns
@@ -339,6 +392,17 @@ mv_status mv_dev_verify_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, ui
 mv_status mv_dev_wal_verify(mv_ctx* ctx, int device, const uint8_t* d_wal, uint64_t size, uint64_t end_pos,
                             uint32_t map_bits, uint64_t* d_pos, uint32_t* d_tag, uint32_t* d_len, uint8_t* d_status,
                             uint64_t cap, uint64_t* count, void* stream);
+/* mv_wal_replay on a WAL image already in HBM (BlockStore::open, block_store.rs:50-116): every array
+ * is device memory, d_summary (3 words) and d_last_seen (committee size words) included; *count
+ * and *n_blocks are written on the host. d_wal is 8-byte aligned and 16 bytes past `size` are
+ * readable (the block path's contract, as mv_dev_verify_blocks; MV_E_INVALID_ARG for a misaligned
+ * pointer). Nothing is written past the first min(*count, cap) entries and min(*n_blocks,
+ * cap_blocks) rows. Synchronises `stream`, as mv_dev_wal_verify does. */
+mv_status mv_dev_wal_replay(mv_ctx* ctx, int device, const uint8_t* d_wal, uint64_t size, uint64_t end_pos,
+                            uint32_t map_bits, uint64_t* d_pos, uint32_t* d_tag, uint32_t* d_len, uint8_t* d_status,
+                            uint64_t cap, uint64_t* count, uint64_t* d_blk_rows, uint8_t* d_blk_status,
+                            uint64_t cap_blocks, uint64_t* n_blocks, uint64_t* d_summary, uint64_t* d_last_seen,
+                            void* stream);
 /* mv_verify_frames on received bytes already in HBM (handle_read_stream, the NetworkMessage decode
  * and process_blocks as there: network.rs:400-457, net_sync.rs:314-383): d_buf, d_soff, d_slen
  * and every output array are device memory; *n_msgs and *n_blocks are written on the host.

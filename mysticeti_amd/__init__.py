@@ -13,6 +13,10 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.blake2b256        BlockHasher (crypto.rs:34)
   Engine.crc32             crc32fast::hash as the WAL uses it (wal.rs:173-177, :250)
   Engine.wal_verify        WalReader::iter_until / WalIterator over try_read (wal.rs:226-346)
+  Engine.wal_replay        the replay loop of BlockStore::open (block_store.rs:50-116): entries, one
+                           row per decoded block with its verify status, highest_round,
+                           last_seen_by_authority
+  Engine.dev_wal_replay    the same on an image already in HBM
   Engine.wal_iter_until    the same as the reference's iterator: (pos, (tag, bytes)), raising
                            where the reference panics
   wal_layout               WalWriter::writev positions (wal.rs:150-188)
@@ -55,9 +59,13 @@ EXPORTS = [
     "mv_set_stage_timing", "mv_stage_times", "mv_dev_verify_blocks", "mv_batch_counters", "mv_batch_routes", "mv_set_batch_groups",
     "mv_queue_stats", "mv_shard_plan", "mv_crc32", "mv_wal_verify", "mv_wal_layout", "mv_dev_wal_verify",
     "mv_frame_blocks", "mv_frame_messages", "mv_verify_frames", "mv_dev_verify_frames",
-    "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
+    "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
+# ... and of the replay loop of BlockStore::open (mv_wal_replay only)
+WAL_UNKNOWN_TAG, WAL_BLOCK_DECODE, WAL_UNKNOWN_AUTHORITY = 4, 5, 6
+WAL_NONE = 0xFFFFFFFFFFFFFFFF  # mv_wal_replay: no such row / entry, next_entry of a tag-1 row
+WAL_ROW_WORDS = 10
 # per-message verdicts (mv_verify_frames rows, word 6's low byte) and the rows' "none" word
 MSG_STATUS = ["OK", "DECODE_ERROR", "BLOCK_REJECTED", "TOO_MANY_REQUESTED", "NOT_REACHED", "BAD_SIZE"]
 MSG_OK, MSG_DECODE_ERROR, MSG_BLOCK_REJECTED, MSG_TOO_MANY_REQUESTED, MSG_NOT_REACHED, MSG_BAD_SIZE = range(6)
@@ -131,6 +139,9 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_verify_frames.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64,
                                          vp, vp]
     lib.mv_dev_wal_verify.argtypes = [vp, ctypes.c_int, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp]
+    lib.mv_wal_replay.argtypes = [vp, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp]
+    lib.mv_dev_wal_replay.argtypes = [vp, ctypes.c_int, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp,
+                                      vp, vp]
     lib.mv_dev_crc32.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, vp, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     lib.mv_host_free.argtypes = [vp, vp]
@@ -177,6 +188,7 @@ class Engine:
             raise MvError(f"mv_create failed ({rc}): no usable gfx950 device")
         self.ctx = h
         self.devices = list(devices)
+        self.committee_size = 0  # authorities of the committee in force (set_committee)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -246,6 +258,7 @@ class Engine:
         ok = np.zeros(pks.shape[0], dtype=np.uint8)
         self._check(self.lib.mv_set_committee(self.ctx, _p(pks), _p(stakes), pks.shape[0], epoch, _p(ok)),
                     "mv_set_committee")
+        self.committee_size = pks.shape[0]
         return ok
 
     # ---- hashes ----
@@ -519,6 +532,56 @@ class Engine:
                                                ctypes.c_void_p(stream_handle or None)), "mv_dev_wal_verify")
         return cnt.value
 
+    def wal_replay(self, image, end_pos: Optional[int] = None, map_bits: int = WAL_MAP_BITS,
+                   cap: Optional[int] = None, cap_blocks: Optional[int] = None) -> "WalReplay":
+        """The replay loop of BlockStore::open (mv_wal_replay, block_store.rs:50-116) over a WAL image
+        (bytes / uint8 array) up to the writer position end_pos (default: its length). Needs
+        set_committee. Returns a WalReplay: the entries as wal_verify gives them (the last one
+        failing where the reference panics: also an unknown tag, a block that does not decode, an
+        authority outside the committee), one row per decoded block with its StatementBlock::verify
+        status, the summary words and last_seen_by_authority. cap / cap_blocks below the totals:
+        only that many entries / rows are returned (count and n_blocks are always the totals)."""
+        img = np.ascontiguousarray(np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray))
+                                   else np.asarray(image, dtype=np.uint8))
+        size = img.size
+        end = size if end_pos is None else int(end_pos)
+        if cap is None:
+            cap = size // 16 + 1
+        if cap_blocks is None:
+            cap_blocks = size // 72 + 1  # a block entry: header 16 + its own reference 56 at least
+        n_auth = self.committee_size
+        pos = np.zeros(max(cap, 1), dtype=np.uint64)
+        tag = np.zeros(max(cap, 1), dtype=np.uint32)
+        ln = np.zeros(max(cap, 1), dtype=np.uint32)
+        st = np.zeros(max(cap, 1), dtype=np.uint8)
+        rows = np.zeros((max(cap_blocks, 1), WAL_ROW_WORDS), dtype=np.uint64)
+        bst = np.zeros(max(cap_blocks, 1), dtype=np.uint8)
+        summary = np.zeros(3, dtype=np.uint64)
+        seen = np.zeros(max(n_auth, 1), dtype=np.uint64)
+        cnt, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.lib.mv_wal_replay(self.ctx, _p(img) if size else None, size, end, map_bits, _p(pos), _p(tag),
+                                           _p(ln), _p(st), cap, ctypes.byref(cnt), _p(rows), _p(bst), cap_blocks,
+                                           ctypes.byref(nb), _p(summary), _p(seen)), "mv_wal_replay")
+        n, b = min(cnt.value, cap), min(nb.value, cap_blocks)
+        return WalReplay(pos[:n], tag[:n], ln[:n], st[:n], rows[:b], bst[:b], summary, seen[:n_auth], cnt.value, nb.value)
+
+    def dev_wal_replay(self, device: int, d_img, size: int, end_pos: int, map_bits: int, d_pos, d_tag, d_len,
+                       d_status, d_rows, d_blk_status, d_summary, d_last_seen, stream_handle: int = 0,
+                       img_ptr: Optional[int] = None) -> Tuple[int, int]:
+        """mv_dev_wal_replay on torch device tensors (d_img uint8, 8-byte aligned with 16 readable
+        bytes past size; d_pos int64, d_tag / d_len int32, d_status uint8 of cap entries; d_rows
+        (cap_blocks x 10) int64; d_blk_status uint8 or None; d_summary (3) and d_last_seen (committee
+        size) int64). Synchronises the stream; returns the (entry, row) totals, of which the first
+        d_pos.shape[0] / d_rows.shape[0] are written. img_ptr overrides d_img's address."""
+        cnt, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._check(self.lib.mv_dev_wal_replay(
+            self.ctx, device, ctypes.c_void_p(img_ptr) if img_ptr is not None else ptr(d_img), size, end_pos, map_bits,
+            ptr(d_pos), ptr(d_tag), ptr(d_len), ptr(d_status), d_pos.shape[0], ctypes.byref(cnt), ptr(d_rows),
+            ptr(d_blk_status) if d_blk_status is not None else None, d_rows.shape[0], ctypes.byref(nb), ptr(d_summary),
+            ptr(d_last_seen), ctypes.c_void_p(stream_handle or None)), "mv_dev_wal_replay")
+        return cnt.value, nb.value
+
     def dev_crc32(self, device: int, d_buf, d_off, d_len, n: int, d_out, stream_handle: int = 0):
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         self._check(self.lib.mv_dev_crc32(self.ctx, device, ptr(d_buf), ptr(d_off), ptr(d_len), n, ptr(d_out),
@@ -587,6 +650,25 @@ def frame_blocks(buf) -> Tuple[np.ndarray, np.ndarray, int]:
     lens = np.zeros(max(n, 1), dtype=np.uint64)
     lib.mv_frame_blocks(_p(b) if b.size else None, b.size, _p(offs), _p(lens), n, ctypes.byref(consumed))
     return offs[:n], lens[:n], int(consumed.value)
+
+
+class WalReplay:
+    """Result of Engine.wal_replay (include/mysti_verify.h, mv_wal_replay). pos / tag / len / status:
+    the entries in iteration order; rows: (n, 10) uint64 block rows (entry index, offset and length
+    of the block's bincode, authority, round, the four digest words, next_entry or WAL_NONE);
+    blk_status: MV_BLOCK_* per row; summary: highest_round, last own row, last state entry (or
+    WAL_NONE); last_seen: per authority. count / n_blocks: the totals (above the array lengths when
+    a cap cut them)."""
+
+    def __init__(self, pos, tag, len, status, rows, blk_status, summary, last_seen, count, n_blocks):
+        self.pos, self.tag, self.len, self.status = pos, tag, len, status
+        self.rows, self.blk_status, self.summary, self.last_seen = rows, blk_status, summary, last_seen
+        self.count, self.n_blocks = count, n_blocks
+
+    @property
+    def digests(self) -> np.ndarray:
+        """(n, 32) uint8: the stored digest of every row's block."""
+        return np.ascontiguousarray(self.rows[:, 5:9]).view(np.uint8).reshape(-1, 32)
 
 
 class FrameVerdicts:

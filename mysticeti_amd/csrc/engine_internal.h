@@ -150,9 +150,12 @@ struct Device {
   } pass;
 
   // WAL replay (wal.hip): crc tables, walk records, per-map counts / flags / offsets, entries,
-  // the image and outputs of host-buffer calls
+  // the image and outputs of host-buffer calls (mv_wal_replay keeps its whole entry list in them)
   struct Wal {
     DevBuf tab, rec, mcount, mflag, moff, ent, ff, img, pos, tag, len, st;
+    // mv_wal_replay (replay.hip): control words, per-workgroup scans and the block lists, the
+    // block rows, and the summary / last_seen of host-buffer calls
+    DevBuf rctl, rscr, rows, rsum;
   } wal;
 
   // mv_verify_frames (frames.hip): per-stream and per-frame walk arrays, the row and block

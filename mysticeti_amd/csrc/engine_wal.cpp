@@ -1,9 +1,11 @@
-// libmysti_verify.so: WAL replay and the crc32 calls (they share the WAL path's crc tables).
+// libmysti_verify.so: the WAL calls -- the entry walk and crc check, the replay up to the block-store
+// index on top of them -- and the crc32 calls (they share the WAL path's crc tables).
 #include <string.h>
 
 #include <algorithm>
 
 #include "engine_internal.h"
+#include "wal_entry.h"
 
 using namespace mvi;
 
@@ -142,6 +144,192 @@ mv_status mv_dev_wal_verify(mv_ctx* ctx, int device, const uint8_t* d_wal, uint6
   HIPCHK(ctx, hipSetDevice(dev->id));
   hipStream_t s = stream ? (hipStream_t)stream : dev->stream;
   return wal_run(ctx, *dev, d_wal, size, end_pos, map_bits, d_pos, d_tag, d_len, d_status, cap, count, s);
+}
+
+// ---------------------------------------------------------------- WAL replay up to the index
+namespace {
+constexpr size_t rp_al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Where replay_run leaves its results (device memory of dev.wal)
+struct ReplayOut {
+  uint64_t count = 0, n_rows = 0;
+  const uint64_t* pos = nullptr;
+  const uint32_t *tag = nullptr, *len = nullptr;
+  const uint8_t* st = nullptr;
+  const uint64_t* rows = nullptr;
+  const uint8_t* blk_status = nullptr;
+};
+
+// wal_run into the device's own entry arrays, then the replay kernels and the block pipeline on
+// the blocks they list (in place in d_img), on stream s. d_summary (3) and d_last_seen (committee
+// size) are written on the device. Synchronises s: wal_run does, the block count sizes the
+// pipeline's launches, and the two counts end the call.
+mv_status replay_run(mv_ctx* ctx, Device& dev, const uint8_t* d_img, uint64_t size, uint64_t end_pos, uint32_t map_bits,
+                     uint64_t* d_summary, uint64_t* d_last_seen, hipStream_t s, ReplayOut& out) {
+  out = ReplayOut();
+  const uint32_t n_auth = ctx->committee.size();
+  // the walk bounds the entry count by size / 16
+  const uint64_t ocap = size / 16 + 1;
+  HIPCHK(ctx, dev.wal.pos.ensure(8 * ocap + 8));
+  HIPCHK(ctx, dev.wal.tag.ensure(4 * ocap + 4));
+  HIPCHK(ctx, dev.wal.len.ensure(4 * ocap + 4));
+  HIPCHK(ctx, dev.wal.st.ensure(ocap + 1));
+  uint64_t n = 0;
+  mv_status st = wal_run(ctx, dev, d_img, size, end_pos, map_bits, dev.wal.pos.as<uint64_t>(), dev.wal.tag.as<uint32_t>(),
+                         dev.wal.len.as<uint32_t>(), dev.wal.st.as<uint8_t>(), ocap, &n, s);
+  if (st != MV_OK) return st;
+  n = std::min(n, ocap);
+  // control words | counts
+  HIPCHK(ctx, dev.wal.rctl.ensure(8 * (mvk::REPLAY_CTL_WORDS + 2)));
+  uint64_t* ctl = dev.wal.rctl.as<uint64_t>();
+  uint64_t* counts = ctl + mvk::REPLAY_CTL_WORDS;
+  HIPCHK(ctx, hipMemsetAsync(ctl, 0, 8 * (mvk::REPLAY_CTL_WORDS + 2), s));
+  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::REPLAY_CTL_FF, 0xff, 8, s));
+  HIPCHK(ctx, hipMemsetAsync(d_last_seen, 0, 8 * (size_t)n_auth, s));
+  const mvk::ReplayEntries en{dev.wal.pos.as<uint64_t>(), dev.wal.tag.as<uint32_t>(), dev.wal.len.as<uint32_t>(),
+                              dev.wal.st.as<uint8_t>(), n};
+  mvk::ReplayBlocks bl{};
+  if (n) {
+    // per workgroup: count | base; per entry (the lists' bound): off | len | ent | block status
+    const size_t nwg = mvk::replay_groups(n), a64 = rp_al(8 * n);
+    const size_t o_base = rp_al(4 * nwg), o_list = o_base + rp_al(8 * nwg);
+    HIPCHK(ctx, dev.wal.rscr.ensure(o_list + 3 * a64 + rp_al(n)));
+    char* b = dev.wal.rscr.as<char>();
+    uint64_t* wgbase = (uint64_t*)(b + o_base);
+    bl = mvk::ReplayBlocks{(uint64_t*)(b + o_list), (uint64_t*)(b + o_list + a64), (uint64_t*)(b + o_list + 2 * a64),
+                           (uint8_t*)(b + o_list + 3 * a64), 0, n};
+    HIPCHK(ctx, mvk::launch_replay_select(en, size, (uint32_t*)b, wgbase, ctl + mvk::REPLAY_CTL_NB, s));
+    uint64_t nb = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&nb, ctl + mvk::REPLAY_CTL_NB, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    bl.n = std::min(nb, n);
+    if (bl.n) {
+      HIPCHK(ctx, mvk::launch_replay_list(en, size, wgbase, bl, s));
+      HIPCHK(ctx, dev.wal.rows.ensure(8 * (size_t)mv::we::ROW_WORDS * bl.n));
+      // the block path as mv_dev_verify_blocks runs it, in chunks of at most max_batch blocks
+      for (uint64_t i = 0; i < bl.n;) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(bl.n - i, ctx->max_batch);
+        st = enqueue_blocks(ctx, dev, d_img, size, bl.off + i, bl.len + i, m, bl.status + i, nullptr, nullptr, s);
+        if (st != MV_OK) {
+          (void)hipStreamSynchronize(s);
+          return st;
+        }
+        i += m;
+      }
+      HIPCHK(ctx, mvk::launch_replay_rows(d_img, en, bl, n_auth, dev.wal.rows.as<uint64_t>(), s));
+    }
+  }
+  HIPCHK(ctx, mvk::launch_replay_summary(en, bl, dev.wal.rows.as<uint64_t>(), n_auth, ctl, d_summary, d_last_seen,
+                                         counts, s));
+  uint64_t h_counts[2] = {0, 0};
+  HIPCHK(ctx, hipMemcpyAsync(h_counts, counts, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  poll_flags(ctx, dev);
+  out.count = std::min(h_counts[0], n);
+  out.n_rows = std::min(h_counts[1], bl.n);
+  out.pos = en.pos;
+  out.tag = en.tag;
+  out.len = en.len;
+  out.st = en.status;
+  out.rows = dev.wal.rows.as<uint64_t>();
+  out.blk_status = bl.status;
+  return MV_OK;
+}
+
+bool replay_args_ok(const void* img, uint64_t size, uint32_t map_bits, const void* pos, const void* tag, const void* len,
+                    const void* status, uint64_t cap, const void* count, const void* rows, uint64_t cap_blocks,
+                    const void* n_blocks, const void* summary, const void* last_seen) {
+  return count && n_blocks && summary && last_seen && !(size && !img) && !(cap && (!pos || !tag || !len || !status)) &&
+         !(cap_blocks && !rows) && wal_args_ok(map_bits);
+}
+}  // namespace
+
+mv_status mv_wal_replay(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
+                        uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap, uint64_t* count,
+                        uint64_t* blk_rows, uint8_t* blk_status, uint64_t cap_blocks, uint64_t* n_blocks,
+                        uint64_t* summary, uint64_t* last_seen) {
+  if (!ctx || !replay_args_ok(wal, size, map_bits, pos, tag, len, status, cap, count, blk_rows, cap_blocks, n_blocks,
+                              summary, last_seen))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad wal replay args");
+  *count = 0;
+  *n_blocks = 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!committee_ready(ctx)) return set_err(ctx, MV_E_NO_COMMITTEE, "mv_set_committee first");
+  Device& dev = ctx->devs[0];  // one image, one device
+  HIPCHK(ctx, hipSetDevice(dev.id));
+  reap_idle(ctx, dev);
+  hipStream_t s = dev.stream;
+  const uint32_t n_auth = ctx->committee.size();
+  HIPCHK(ctx, dev.wal.img.ensure(size + 16));
+  if (size) HIPCHK(ctx, hipMemcpyAsync(dev.wal.img.p, wal, size, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemsetAsync(dev.wal.img.as<uint8_t>() + size, 0, 16, s));  // the readable bytes past the last block
+  HIPCHK(ctx, dev.wal.rsum.ensure(8 * (3 + (size_t)n_auth)));
+  uint64_t* d_summary = dev.wal.rsum.as<uint64_t>();
+  ReplayOut ro;
+  const mv_status st = replay_run(ctx, dev, dev.wal.img.as<uint8_t>(), size, end_pos, map_bits, d_summary, d_summary + 3,
+                                  s, ro);
+  if (st != MV_OK) {
+    (void)hipStreamSynchronize(s);  // (the image copy may still be in flight)
+    return st;
+  }
+  const uint64_t w = std::min(ro.count, cap), wr = std::min(ro.n_rows, cap_blocks);
+  if (w) {
+    HIPCHK(ctx, hipMemcpyAsync(pos, ro.pos, 8 * w, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(tag, ro.tag, 4 * w, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(len, ro.len, 4 * w, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(status, ro.st, w, hipMemcpyDeviceToHost, s));
+  }
+  if (wr) {
+    HIPCHK(ctx, hipMemcpyAsync(blk_rows, ro.rows, 8 * (size_t)mv::we::ROW_WORDS * wr, hipMemcpyDeviceToHost, s));
+    if (blk_status) HIPCHK(ctx, hipMemcpyAsync(blk_status, ro.blk_status, wr, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(ctx, hipMemcpyAsync(summary, d_summary, 24, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(last_seen, d_summary + 3, 8 * (size_t)n_auth, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  *count = ro.count;
+  *n_blocks = ro.n_rows;
+  return MV_OK;
+}
+
+mv_status mv_dev_wal_replay(mv_ctx* ctx, int device, const uint8_t* d_wal, uint64_t size, uint64_t end_pos,
+                            uint32_t map_bits, uint64_t* d_pos, uint32_t* d_tag, uint32_t* d_len, uint8_t* d_status,
+                            uint64_t cap, uint64_t* count, uint64_t* d_blk_rows, uint8_t* d_blk_status,
+                            uint64_t cap_blocks, uint64_t* n_blocks, uint64_t* d_summary, uint64_t* d_last_seen,
+                            void* stream) {
+  if (!ctx || !replay_args_ok(d_wal, size, map_bits, d_pos, d_tag, d_len, d_status, cap, count, d_blk_rows, cap_blocks,
+                              n_blocks, d_summary, d_last_seen))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad wal replay args");
+  if (((uintptr_t)d_wal) & 7) return set_err(ctx, MV_E_INVALID_ARG, "d_wal must be 8-byte aligned");
+  *count = 0;
+  *n_blocks = 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!committee_ready(ctx)) return set_err(ctx, MV_E_NO_COMMITTEE, "mv_set_committee first");
+  Device* dev = find_dev(ctx, device);
+  if (!dev) return set_err(ctx, MV_E_NO_DEVICE, "device not in context");
+  HIPCHK(ctx, hipSetDevice(dev->id));
+  reap_idle(ctx, *dev);
+  hipStream_t s = stream ? (hipStream_t)stream : dev->stream;
+  ReplayOut ro;
+  const mv_status st = replay_run(ctx, *dev, d_wal, size, end_pos, map_bits, d_summary, d_last_seen, s, ro);
+  if (st != MV_OK) {
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  const uint64_t w = std::min(ro.count, cap), wr = std::min(ro.n_rows, cap_blocks);
+  if (w) {
+    HIPCHK(ctx, hipMemcpyAsync(d_pos, ro.pos, 8 * w, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_tag, ro.tag, 4 * w, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_len, ro.len, 4 * w, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_status, ro.st, w, hipMemcpyDeviceToDevice, s));
+  }
+  if (wr) {
+    HIPCHK(ctx, hipMemcpyAsync(d_blk_rows, ro.rows, 8 * (size_t)mv::we::ROW_WORDS * wr, hipMemcpyDeviceToDevice, s));
+    if (d_blk_status) HIPCHK(ctx, hipMemcpyAsync(d_blk_status, ro.blk_status, wr, hipMemcpyDeviceToDevice, s));
+  }
+  if (w || wr) HIPCHK(ctx, hipStreamSynchronize(s));
+  *count = ro.count;
+  *n_blocks = ro.n_rows;
+  return MV_OK;
 }
 
 uint64_t mv_wal_layout(const uint64_t* payload_len, uint64_t n, uint32_t map_bits, uint64_t start, uint64_t* pos) {

@@ -318,6 +318,41 @@ hipError_t launch_wal_compact(const unsigned long long* rec, uint32_t cap_pm, co
 hipError_t launch_wal_crc(const uint8_t* img, uint64_t size, const unsigned long long* ent, uint64_t total,
                           const uint32_t* tables, uint64_t* out_pos, uint32_t* out_tag, uint32_t* out_len,
                           uint8_t* out_status, uint64_t cap, unsigned long long* first_fail, int cus, hipStream_t s);
+// replay.hip: mv_wal_replay after the walk and the crc pass (rules: wal_entry.h). The entry list is
+// launch_wal_crc's output in device memory; entry statuses are updated in place.
+struct ReplayEntries {
+  const uint64_t* pos;
+  const uint32_t* tag;
+  const uint32_t* len;
+  uint8_t* status;
+  uint64_t n;  // the walk's entries up to and including its first failing one
+};
+struct ReplayBlocks {  // the entries that carry a block, in iteration order (lists of cap >= n places)
+  uint64_t* off;       // of the block's bincode in the image
+  uint64_t* len;
+  uint64_t* ent;       // entry index
+  uint8_t* status;     // MV_BLOCK_* (enqueue_blocks)
+  uint64_t n, cap;
+};
+// control words (device): the block total, the first failing entry (preset to all ones), the rows
+// kept, three maxima (highest round, last own row + 1, last state entry + 1); the rest preset to 0
+constexpr int REPLAY_CTL_NB = 0, REPLAY_CTL_FF = 1, REPLAY_CTL_NROWS = 2, REPLAY_CTL_ACC = 3, REPLAY_CTL_WORDS = 6;
+uint64_t replay_groups(uint64_t n);  // workgroups of the per-entry kernels: wgcount / wgbase hold one word each
+// k_replay_select + k_replay_scan: statuses of unknown tags and short own-block payloads, the
+// per-workgroup block counts and their scan, *nb = the block total
+hipError_t launch_replay_select(const ReplayEntries& en, uint64_t size, uint32_t* wgcount, uint64_t* wgbase,
+                                uint64_t* nb, hipStream_t s);
+hipError_t launch_replay_list(const ReplayEntries& en, uint64_t size, const uint64_t* wgbase, const ReplayBlocks& bl,
+                              hipStream_t s);
+// one lane per listed block: its row (10 words), or its entry's MV_WAL_BLOCK_DECODE /
+// MV_WAL_UNKNOWN_AUTHORITY
+hipError_t launch_replay_rows(const uint8_t* img, const ReplayEntries& en, const ReplayBlocks& bl, uint32_t n_auth,
+                              uint64_t* rows, hipStream_t s);
+// k_replay_cut, k_replay_summary, k_replay_finish: summary[3], last_seen[n_auth] (preset to 0),
+// counts = {entries, rows} after the cut at the first entry that is not OK
+hipError_t launch_replay_summary(const ReplayEntries& en, const ReplayBlocks& bl, const uint64_t* rows, uint32_t n_auth,
+                                 uint64_t* ctl, uint64_t* summary, uint64_t* last_seen, uint64_t* counts,
+                                 hipStream_t s);
 // frames.hip: the walk of received NetworkMessage frames and the per-message / per-connection
 // verdicts of mv_verify_frames (rules: frame_walk.h). Stream s = buf[soff[s], soff[s] + slen[s])
 // clipped to buf_bytes. Count / scan / list as the WAL walk: the first launch_frame_walk

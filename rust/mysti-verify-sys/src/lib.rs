@@ -46,6 +46,9 @@ pub const MV_WAL_OK: u8 = 0;
 pub const MV_WAL_CRC_MISMATCH: u8 = 1;
 pub const MV_WAL_NONZERO_CRC_LEN0: u8 = 2;
 pub const MV_WAL_BAD_LENGTH: u8 = 3;
+pub const MV_WAL_UNKNOWN_TAG: u8 = 4;
+pub const MV_WAL_BLOCK_DECODE: u8 = 5;
+pub const MV_WAL_UNKNOWN_AUTHORITY: u8 = 6;
 
 pub const MV_MSG_OK: u32 = 0;
 pub const MV_MSG_DECODE_ERROR: u32 = 1;
@@ -87,6 +90,10 @@ extern "C" {
     pub fn mv_wal_verify(ctx: *mut mv_ctx, wal: *const u8, size: u64, end_pos: u64, map_bits: u32,
                          pos: *mut u64, tag: *mut u32, len: *mut u32, status: *mut u8, cap: u64,
                          count: *mut u64) -> i32;
+    pub fn mv_wal_replay(ctx: *mut mv_ctx, wal: *const u8, size: u64, end_pos: u64, map_bits: u32,
+                         pos: *mut u64, tag: *mut u32, len: *mut u32, status: *mut u8, cap: u64,
+                         count: *mut u64, blk_rows: *mut u64, blk_status: *mut u8, cap_blocks: u64,
+                         n_blocks: *mut u64, summary: *mut u64, last_seen: *mut u64) -> i32;
     pub fn mv_wal_layout(payload_len: *const u64, n: u64, map_bits: u32, start: u64, pos: *mut u64) -> u64;
     pub fn mv_frame_blocks(buf: *const u8, len: u64, off: *mut u64, blen: *mut u64, cap: u64,
                            consumed: *mut u64) -> i64;
@@ -115,6 +122,11 @@ extern "C" {
     pub fn mv_dev_wal_verify(ctx: *mut mv_ctx, device: i32, d_wal: *const u8, size: u64, end_pos: u64,
                              map_bits: u32, d_pos: *mut u64, d_tag: *mut u32, d_len: *mut u32,
                              d_status: *mut u8, cap: u64, count: *mut u64, stream: *mut c_void) -> i32;
+    pub fn mv_dev_wal_replay(ctx: *mut mv_ctx, device: i32, d_wal: *const u8, size: u64, end_pos: u64,
+                             map_bits: u32, d_pos: *mut u64, d_tag: *mut u32, d_len: *mut u32,
+                             d_status: *mut u8, cap: u64, count: *mut u64, d_blk_rows: *mut u64,
+                             d_blk_status: *mut u8, cap_blocks: u64, n_blocks: *mut u64,
+                             d_summary: *mut u64, d_last_seen: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_dev_crc32(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, d_off: *const u64, d_len: *const u64,
                         n: u32, d_out: *mut u32, stream: *mut c_void) -> i32;
     pub fn mv_batch_stats(ctx: *mut mv_ctx, batches: *mut u64, fallbacks: *mut u64) -> i32;

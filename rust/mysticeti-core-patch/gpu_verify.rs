@@ -123,6 +123,56 @@ impl GpuVerifier {
             cap_b = cap_b.max(b);
         }
     }
+
+    /// The replay loop of BlockStore::open (block_store.rs:50-116) over a WAL image, up to the
+    /// writer position `end_pos`: one mv_wal_replay call walks the entries, checks their crc,
+    /// decodes and verifies every WAL_ENTRY_BLOCK / WAL_ENTRY_OWN_BLOCK block in place and returns
+    /// the entries, one row per block (its BlockReference for add_unloaded, next_entry of an own
+    /// block), highest_round, last_seen_by_authority and the positions RecoveredStateBuilder
+    /// wants. The caller still decodes payload, state and commit entries (tags 2, 4, 5) and keeps
+    /// the `pending` map from pos, the tags and next_entry (state.rs:39-59). An entry whose
+    /// status is not MV_WAL_OK -- always the last -- is where the reference panics.
+    pub fn wal_replay(&self, wal: &[u8], end_pos: u64, map_bits: u32, committee_size: usize) -> eyre::Result<WalReplay> {
+        let cap = wal.len() / 16 + 1; // an entry takes at least its 16-byte header
+        let mut out = WalReplay {
+            pos: vec![0; cap],
+            tag: vec![0; cap],
+            len: vec![0; cap],
+            status: vec![0; cap],
+            rows: vec![0; 10 * cap],
+            blk_status: vec![0; cap],
+            summary: [0; 3],
+            last_seen: vec![0; committee_size],
+        };
+        let (mut count, mut n_blocks) = (0u64, 0u64);
+        let rc = unsafe {
+            sys::mv_wal_replay(self.ctx, wal.as_ptr(), wal.len() as u64, end_pos, map_bits, out.pos.as_mut_ptr(),
+                               out.tag.as_mut_ptr(), out.len.as_mut_ptr(), out.status.as_mut_ptr(), cap as u64,
+                               &mut count, out.rows.as_mut_ptr(), out.blk_status.as_mut_ptr(), cap as u64,
+                               &mut n_blocks, out.summary.as_mut_ptr(), out.last_seen.as_mut_ptr())
+        };
+        ensure!(rc == sys::MV_OK, "mv_wal_replay: {}", self.last_error());
+        let (n, b) = (count as usize, n_blocks as usize);
+        out.pos.truncate(n);
+        out.tag.truncate(n);
+        out.len.truncate(n);
+        out.status.truncate(n);
+        out.rows.truncate(10 * b);
+        out.blk_status.truncate(b);
+        Ok(out)
+    }
+}
+
+/// Result of `GpuVerifier::wal_replay` (layout: include/mysti_verify.h, mv_wal_replay).
+pub struct WalReplay {
+    pub pos: Vec<u64>,       // per entry: WalPosition.start
+    pub tag: Vec<u32>,
+    pub len: Vec<u32>,       // payload bytes
+    pub status: Vec<u8>,     // MV_WAL_*; only the last entry can be other than MV_WAL_OK
+    pub rows: Vec<u64>,      // 10 words per block: entry, offset, length, authority, round, digest[4], next_entry
+    pub blk_status: Vec<u8>, // MV_BLOCK_* of StatementBlock::verify (the reference's replay does not verify)
+    pub summary: [u64; 3],   // highest_round, last own row or u64::MAX, last state entry or u64::MAX
+    pub last_seen: Vec<u64>, // last_seen_by_authority
 }
 
 /// Result of `GpuVerifier::verify_frames` (layout: include/mysti_verify.h, mv_verify_frames).
