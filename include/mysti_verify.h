@@ -467,6 +467,22 @@ mv_status mv_get_option(mv_ctx* ctx, const char* name, int64_t* value);
  * Ops >= 64 are the raw-limb field and point test hooks: 64 words in and 64 words out per lane
  * (the row layout is documented at k_selftest_wide in kernels.hip). */
 mv_status mv_selftest(mv_ctx* ctx, int op, const uint32_t* in, uint32_t n, uint32_t* out);
+/* Test entry: the preparation stage of the batch path alone (k_bv_prep, batch.hip), launched by
+ * the helper the production path launches it with, for n signatures in host arrays (msg, sig and
+ * exactly one of pk / key_idx, as mv_ed25519_verify takes them; key_idx needs mv_set_committee).
+ * groups: the sub-batch count asked for (clamped as a verify call's). key: 40 bytes, the 32-byte
+ * secret of the coefficients z_i and the 64-bit call counter. launch_sigs: 0 = one launch, else a
+ * multiple of 256: one launch per launch_sigs signatures, as the chunked copies of pinned inputs
+ * gate them. Out (host): scal n x 12 words (z_i in 4, z_i k_i mod l in 8), pts 2 n x 32 words
+ * (the affine (y+x, y-x, 2dxy) limb rows of R at i and of A at n + i, 27 words each; with a
+ * committee whose A term is summed per key no A row is written: rows n.. stay as they were),
+ * bsum 16 x 12 column sums of z_i s_i per group, status n bytes (MV_SIG_* as the preparation
+ * decides them), info 3 words: groups, signatures per group, 1 if the A rows were written. The
+ * context's call counter, batch counters, guard and route are not touched. */
+mv_status mv_selftest_batch_prep(mv_ctx* ctx, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk,
+                                 const uint32_t* key_idx, uint32_t n, uint32_t groups, const uint8_t* key,
+                                 uint32_t launch_sigs, uint32_t* scal, uint32_t* pts, uint64_t* bsum,
+                                 uint8_t* status, uint32_t* info);
 
 #ifdef __cplusplus
 }

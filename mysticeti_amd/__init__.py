@@ -55,7 +55,7 @@ BLOCK_STATUS = [
 EXPORTS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_version", "mv_set_committee", "mv_blake2b256",
     "mv_ed25519_verify", "mv_ed25519_sign", "mv_verify_blocks", "mv_dev_ed25519_verify",
-    "mv_dev_ed25519_sign", "mv_selftest", "mv_block_preimage", "mv_dev_ed25519_verify_batch", "mv_batch_stats",
+    "mv_dev_ed25519_sign", "mv_selftest", "mv_selftest_batch_prep", "mv_block_preimage", "mv_dev_ed25519_verify_batch", "mv_batch_stats",
     "mv_set_stage_timing", "mv_stage_times", "mv_dev_verify_blocks", "mv_batch_counters", "mv_batch_routes", "mv_set_batch_groups",
     "mv_queue_stats", "mv_shard_plan", "mv_crc32", "mv_wal_verify", "mv_wal_layout", "mv_dev_wal_verify",
     "mv_frame_blocks", "mv_frame_messages", "mv_verify_frames", "mv_dev_verify_frames",
@@ -77,6 +77,8 @@ STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "has
 FLAG_NO_BATCH, FLAG_NO_COMB, FLAG_HOST_PARSE, FLAG_NO_ONLINE = 1, 2, 4, 8
 BATCH_MIN = 4096
 SELFTEST_WIDE_OP = 64  # mv_selftest ops from here on use 64-word rows
+BATCH_MAX_GROUPS = 16  # sub-batch equations per batch at most
+BATCH_PREP_UNWRITTEN = 0xA5A5A5A5  # Engine.batch_prep: the words of point rows that were not read back
 
 
 class MvError(RuntimeError):
@@ -125,6 +127,7 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_verify_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, vp, vp, vp, vp]
     lib.mv_dev_ed25519_sign.argtypes = [vp, ctypes.c_int, vp, vp, u32, vp, vp, vp]
     lib.mv_selftest.argtypes = [vp, ctypes.c_int, vp, u32, vp]
+    lib.mv_selftest_batch_prep.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     lib.mv_block_preimage.argtypes = [vp, u64, vp, u64]
     lib.mv_block_preimage.restype = ctypes.c_int64
     lib.mv_crc32.argtypes = [vp, vp, vp, vp, u32, vp]
@@ -601,6 +604,29 @@ class Engine:
         self._check(self.lib.mv_selftest(self.ctx, op, _p(w), w.shape[0], _p(out)), "mv_selftest")
         return out
 
+    def batch_prep(self, msg, sig, pk=None, key_idx=None, groups: int = 1, secret: bytes = bytes(32), call: int = 0,
+                   launch_sigs: int = 0) -> "BatchPrep":
+        """The batch path's preparation stage alone (mv_selftest_batch_prep: k_bv_prep launched as
+        a verify call launches it) with the coefficient key (secret, call) given. launch_sigs: 0 =
+        one launch, else signatures per launch (a multiple of 256), as pinned inputs' copy chunks
+        gate them. Returns a BatchPrep."""
+        msg, sig = _u8(msg, 32), _u8(sig, 64)
+        n = msg.shape[0]
+        pk_a = _u8(pk, 32) if pk is not None else None
+        ki = np.ascontiguousarray(np.asarray(key_idx, dtype=np.uint32)) if key_idx is not None else None
+        if len(secret) != 32:
+            raise ValueError("secret: 32 bytes")
+        key = np.frombuffer(bytes(secret) + int(call).to_bytes(8, "little"), dtype=np.uint8)
+        scal = np.zeros((n, 12), dtype=np.uint32)
+        pts = np.full((2 * n, 32), BATCH_PREP_UNWRITTEN, dtype=np.uint32)
+        bsum = np.zeros((BATCH_MAX_GROUPS, 12), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        info = np.zeros(3, dtype=np.uint32)
+        self._check(self.lib.mv_selftest_batch_prep(self.ctx, _p(msg), _p(sig), _p(pk_a), _p(ki), n, int(groups), _p(key),
+                                                    int(launch_sigs), _p(scal), _p(pts), _p(bsum), _p(st), _p(info)),
+                    "mv_selftest_batch_prep")
+        return BatchPrep(scal, pts, bsum, st, int(info[0]), int(info[1]), bool(info[2]))
+
 
 def block_preimage(bincode: bytes) -> Optional[bytes]:
     """Host-side pre-image of one bincode StatementBlock (None if it does not deserialize)."""
@@ -650,6 +676,28 @@ def frame_blocks(buf) -> Tuple[np.ndarray, np.ndarray, int]:
     lens = np.zeros(max(n, 1), dtype=np.uint64)
     lib.mv_frame_blocks(_p(b) if b.size else None, b.size, _p(offs), _p(lens), n, ctypes.byref(consumed))
     return offs[:n], lens[:n], int(consumed.value)
+
+
+class BatchPrep:
+    """Result of Engine.batch_prep (include/mysti_verify.h, mv_selftest_batch_prep). scal: (n, 12)
+    uint32, z_i in words 0..3 and z_i k_i mod l in words 4..11; pts: (2 n, 32) uint32 limb rows (27
+    words: y+x, y-x, 2dxy), R at i and A at n + i (BATCH_PREP_UNWRITTEN words where a_rows is
+    False); bsum: (16, 12) uint64 column sums of z_i s_i per group; status: MV_SIG_* per signature;
+    groups, group_sigs: the geometry the engine used."""
+
+    def __init__(self, scal, pts, bsum, status, groups, group_sigs, a_rows):
+        self.scal, self.pts, self.bsum, self.status = scal, pts, bsum, status
+        self.groups, self.group_sigs, self.a_rows = groups, group_sigs, a_rows
+
+    def z(self, i: int) -> int:
+        return int.from_bytes(self.scal[i, :4].tobytes(), "little")
+
+    def zk(self, i: int) -> int:
+        return int.from_bytes(self.scal[i, 4:].tobytes(), "little")
+
+    def group_sum(self, g: int) -> int:
+        """sum z_i s_i over group g, from its 12 columns (each a sum of 32-bit words)."""
+        return sum(int(c) << (32 * k) for k, c in enumerate(self.bsum[g]))
 
 
 class WalReplay:

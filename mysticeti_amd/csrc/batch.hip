@@ -1460,6 +1460,70 @@ uint32_t batch_group_size(uint32_t n, uint32_t groups) {
   return batch_groups(n, groups).cpg * mv::PART_CHUNK;
 }
 
+namespace {
+// The preparation stage of a batch of n signatures in groups G, the one place it is launched
+// from: the committee set-up (A from the comb tables, its term summed per key or not), the
+// zeroing of the per-group column sums and k_bv_prep, whole or chunk by chunk behind the copy
+// gates. launch_verify_batch continues with the sort from here; launch_batch_prep (the test
+// entry mv_selftest_batch_prep) stops here and reads the outputs back.
+struct PrepStage {
+  mv::CommitteeA ca;
+  bool agg;  // A's term summed per key: no A points, no A bucket entries
+};
+hipError_t launch_prep_stage(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk,
+                             const uint32_t* key_idx, uint32_t n, const mv::BvGroups& G, const uint32_t key[10],
+                             uint4* pts, uint4* scal, unsigned long long* bsum, uint8_t* status, hipStream_t s,
+                             const void* comb_a, const uint8_t* key_ok, uint32_t n_keys, const ChunkGate* gate,
+                             const hipEvent_t* chain, PrepStage* out) {
+  using namespace mv;
+  hipError_t e;
+  BvKey k;
+  for (int i = 0; i < 10; i++) k.w[i] = key[i];
+  // committee keys with their comb tables: A from the tables, and its term summed per key
+  const bool com = key_idx && key_ok && comb_a;
+  const bool agg = com && n_keys > 0 && n_keys <= (uint32_t)BV_MAXKEYS && !agg_disabled(kn);
+  const CommitteeA ca{com ? static_cast<const uint4*>(comb_a) : nullptr, key_ok,
+                      (uint32_t)(comb_table_bytes(1) / sizeof(uint4)), agg ? 1u : 0u};
+  out->ca = ca;
+  out->agg = agg;
+  e = hipMemsetAsync(bsum, 0, (size_t)BV_MAXG * BSUM_WORDS * 8, s);  // k_bv_prep accumulates per group
+  if (e != hipSuccess) return e;
+  const uint32_t group_sigs = G.cpg * PART_CHUNK;
+  if (gate && gate->n) {
+    const uint32_t* end = gate->end;
+    if (end[gate->n - 1] != n) return hipErrorInvalidValue;
+    for (uint32_t c = 0, lo = 0; c < gate->n; lo = end[c++]) {
+      const uint32_t hi = end[c];
+      if (hi <= lo || lo % 256 || (hi % 256 && hi != n)) return hipErrorInvalidValue;
+      if ((e = hipStreamWaitEvent(s, gate->ready[c], 0)) != hipSuccess) return e;
+      hipLaunchKernelGGL(k_bv_prep, dim3((hi - lo + 255) / 256), dim3(256), 0, s, msg, sig, pk, key_idx, n, k, ca,
+                         pts, scal, bsum, status, lo / 256, group_sigs);
+    }
+  } else {
+    if (chain && chain[0] && (e = hipStreamWaitEvent(s, chain[0], 0)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bv_prep, dim3((n + 255) / 256), dim3(256), 0, s, msg, sig, pk, key_idx, n, k, ca, pts, scal,
+                       bsum, status, 0u, group_sigs);
+    if (chain && (e = hipEventRecord(chain[1], s)) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+}  // namespace
+
+hipError_t launch_batch_prep(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk,
+                             const uint32_t* key_idx, uint32_t n, uint32_t groups, const uint32_t key[10], void* pts,
+                             void* scal, void* bsum, uint8_t* status, hipStream_t s, const void* comb_a,
+                             const uint8_t* key_ok, uint32_t n_keys, const ChunkGate* gate, BatchPrepInfo* info) {
+  if (n == 0) return hipSuccess;
+  const mv::BvGroups G = batch_groups(n, groups);
+  PrepStage ps;
+  hipError_t e = launch_prep_stage(kn, msg, sig, pk, key_idx, n, G, key, static_cast<uint4*>(pts),
+                                   static_cast<uint4*>(scal), static_cast<unsigned long long*>(bsum), status, s, comb_a,
+                                   key_ok, n_keys, gate, nullptr, &ps);
+  if (e != hipSuccess) return e;
+  if (info) *info = BatchPrepInfo{G.count, G.cpg * mv::PART_CHUNK, ps.ca.tab && ps.ca.aggregate ? 0u : 1u};
+  return hipGetLastError();
+}
+
 hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* key_idx,
                                uint32_t n, uint32_t groups, const uint32_t key[10], const void* btab,
                                void* bscratch, void* vscratch, uint8_t* status, hipStream_t s,
@@ -1491,21 +1555,17 @@ hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_
   uint4* asum = (uint4*)(base + L.asum);
   uint32_t* flag = (uint32_t*)(base + L.flag);
   if (flag_out) *flag_out = flag;
-  const uint32_t nblk = (n + 255) / 256;
   hipError_t e;
-  BvKey k;
-  for (int i = 0; i < 10; i++) k.w[i] = key[i];
   const uint32_t nchunk = (n + PART_CHUNK - 1) / PART_CHUNK;
   const uint32_t nparts = G.count * BV_NPG;
   mark(0);
-  // committee keys with their comb tables: A from the tables, and its term summed per key
-  const bool com = key_idx && key_ok && comb_a;
-  const bool agg = com && n_keys > 0 && n_keys <= (uint32_t)BV_MAXKEYS && !agg_disabled(kn);
-  CommitteeA ca{com ? static_cast<const uint4*>(comb_a) : nullptr, key_ok,
-                (uint32_t)(comb_table_bytes(1) / sizeof(uint4)), agg ? 1u : 0u};
-  const uint32_t nw = agg ? BV_NWR : BV_NW;  // windows with bucket entries
-  e = hipMemsetAsync(bsum, 0, (size_t)BV_MAXG * BSUM_WORDS * 8, s);  // k_bv_prep accumulates per group
+  PrepStage ps;
+  e = launch_prep_stage(kn, msg, sig, pk, key_idx, n, G, key, pts, scal, bsum, status, s, comb_a, key_ok, n_keys, gate,
+                        chain, &ps);
   if (e != hipSuccess) return e;
+  const CommitteeA& ca = ps.ca;
+  const bool agg = ps.agg;
+  const uint32_t nw = agg ? BV_NWR : BV_NW;  // windows with bucket entries
   const uint32_t seg = bucket_segment(kn);
   const uint32_t nk = G.count * BV_NKG;
   // bucket sums of the sorted entries of m signatures
@@ -1527,22 +1587,6 @@ hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_
                          G.count, seg, nw, segV, segT);
     }
   };
-  if (gate && gate->n) {
-    const uint32_t* end = gate->end;
-    if (end[gate->n - 1] != n) return hipErrorInvalidValue;
-    for (uint32_t c = 0, lo = 0; c < gate->n; lo = end[c++]) {
-      const uint32_t hi = end[c];
-      if (hi <= lo || lo % 256 || (hi % 256 && hi != n)) return hipErrorInvalidValue;
-      if ((e = hipStreamWaitEvent(s, gate->ready[c], 0)) != hipSuccess) return e;
-      hipLaunchKernelGGL(k_bv_prep, dim3((hi - lo + 255) / 256), dim3(256), 0, s, msg, sig, pk, key_idx, n, k, ca,
-                         pts, scal, bsum, status, lo / 256, G.cpg * PART_CHUNK);
-    }
-  } else {
-    if (chain && chain[0] && (e = hipStreamWaitEvent(s, chain[0], 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bv_prep, dim3(nblk), dim3(256), 0, s, msg, sig, pk, key_idx, n, k, ca, pts, scal, bsum,
-                       status, 0u, G.cpg * PART_CHUNK);
-    if (chain && (e = hipEventRecord(chain[1], s)) != hipSuccess) return e;
-  }
   {
     mark(1);
     hipLaunchKernelGGL(k_part_count, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, agg ? 1u : 0u, pcount);

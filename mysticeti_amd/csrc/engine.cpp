@@ -1202,4 +1202,78 @@ mv_status mv_selftest(mv_ctx* ctx, int op, const uint32_t* in, uint32_t n, uint3
   return MV_OK;
 }
 
+mv_status mv_selftest_batch_prep(mv_ctx* ctx, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk,
+                                 const uint32_t* key_idx, uint32_t n, uint32_t groups, const uint8_t* key,
+                                 uint32_t launch_sigs, uint32_t* scal, uint32_t* pts, uint64_t* bsum,
+                                 uint8_t* status, uint32_t* info) {
+  if (!ctx || !key || !bsum || !info || (n && (!msg || !sig || !scal || !pts || !status || (!pk == !key_idx))))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad batch prep args: exactly one of pk / key_idx");
+  if (launch_sigs % 256) return set_err(ctx, MV_E_INVALID_ARG, "launch_sigs must be a multiple of 256");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device& dev = ctx->devs[0];
+  if (key_idx) {
+    if (!ctx->has_committee || !dev.committee_loaded)
+      return set_err(ctx, MV_E_NO_COMMITTEE, "key_idx given but no committee set");
+    for (uint32_t i = 0; i < n; i++)
+      if (key_idx[i] >= ctx->committee.size()) return set_err(ctx, MV_E_INVALID_ARG, "key_idx out of range");
+  }
+  info[0] = info[1] = info[2] = 0;
+  memset(bsum, 0, sizeof(uint64_t) * 12 * mvk::BATCH_MAX_GROUPS);
+  if (n == 0) return MV_OK;
+  HIPCHK(ctx, hipSetDevice(dev.id));
+  // buffers of this call alone (released on return): the engine's own scratch, its counters, the
+  // call counter, the guard and the route stay as they are
+  constexpr size_t kPtRow = 128, kScRow = 48;
+  const size_t bsum_bytes = sizeof(uint64_t) * 12 * mvk::BATCH_MAX_GROUPS;
+  mvr::DevBuf d_msg, d_sig, d_pk, d_pts, d_scal, d_bsum, d_status;
+  mvr::Event ready;
+  HIPCHK(ctx, d_msg.ensure(32 * (size_t)n));
+  HIPCHK(ctx, d_sig.ensure(64 * (size_t)n));
+  HIPCHK(ctx, d_pk.ensure((pk ? 32 : 4) * (size_t)n));
+  HIPCHK(ctx, d_pts.ensure(2 * kPtRow * (size_t)n));
+  HIPCHK(ctx, d_scal.ensure(kScRow * (size_t)n));
+  HIPCHK(ctx, d_bsum.ensure(bsum_bytes));
+  HIPCHK(ctx, d_status.ensure(n));
+  HIPCHK(ctx, ready.ensure());
+  hipStream_t s = dev.stream;
+  HIPCHK(ctx, hipMemcpyAsync(d_msg.p, msg, 32 * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(d_sig.p, sig, 64 * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(d_pk.p, pk ? (const void*)pk : key_idx, (pk ? 32 : 4) * (size_t)n, hipMemcpyHostToDevice, s));
+  // what the kernel does not write reads back as 0xff.. (unwritten rows show)
+  HIPCHK(ctx, hipMemsetAsync(d_pts.p, 0xff, 2 * kPtRow * (size_t)n, s));
+  HIPCHK(ctx, hipMemsetAsync(d_scal.p, 0xff, kScRow * (size_t)n, s));
+  HIPCHK(ctx, hipMemsetAsync(d_status.p, 0xff, n, s));
+  HIPCHK(ctx, hipMemsetAsync(d_bsum.p, 0xff, bsum_bytes, s));
+  uint32_t kw[10];
+  memcpy(kw, key, 40);
+  // launch_sigs > 0: the chunked launches of the pinned path (one per copy chunk, behind its event)
+  std::vector<uint32_t> ends;
+  std::vector<hipEvent_t> evs;
+  if (launch_sigs)
+    for (uint64_t o = launch_sigs;; o += launch_sigs) {
+      ends.push_back((uint32_t)std::min<uint64_t>(o, n));
+      evs.push_back(ready);
+      if (o >= n) break;
+    }
+  HIPCHK(ctx, hipEventRecord(ready, s));
+  const mvk::ChunkGate gate{evs.data(), (uint32_t)ends.size(), ends.data()};
+  const bool com_a = key_idx && !(ctx->flags & MV_FLAG_NO_COMB);
+  mvk::BatchPrepInfo pi{};
+  HIPCHK(ctx, mvk::launch_batch_prep(ctx->kn, d_msg.as<uint8_t>(), d_sig.as<uint8_t>(),
+                                     pk ? d_pk.as<uint8_t>() : dev.tab.committee_pk.as<uint8_t>(),
+                                     pk ? nullptr : d_pk.as<uint32_t>(), n, groups, kw, d_pts.p, d_scal.p, d_bsum.p,
+                                     d_status.as<uint8_t>(), s, com_a ? dev.tab.combA.p : nullptr,
+                                     com_a ? dev.tab.keyok.as<uint8_t>() : nullptr,
+                                     com_a ? (uint32_t)ctx->committee.size() : 0u, launch_sigs ? &gate : nullptr, &pi));
+  HIPCHK(ctx, hipMemcpyAsync(scal, d_scal.p, kScRow * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(pts, d_pts.p, (pi.a_rows ? 2 : 1) * kPtRow * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(bsum, d_bsum.p, bsum_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(status, d_status.p, n, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  info[0] = pi.groups;
+  info[1] = pi.group_sigs;
+  info[2] = pi.a_rows;
+  return MV_OK;
+}
+
 }  // extern "C"

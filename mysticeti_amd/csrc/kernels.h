@@ -116,6 +116,19 @@ hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_
                                uint32_t** flag_out, hipEvent_t* ev = nullptr, const void* comb_a = nullptr,
                                const uint8_t* key_ok = nullptr, uint32_t n_keys = 0, const void* comb_b = nullptr,
                                const struct ChunkGate* gate = nullptr, const hipEvent_t* chain = nullptr);
+// The preparation stage alone (the test entry mv_selftest_batch_prep): the zeroing of the column
+// sums and the k_bv_prep launch(es), by the helper launch_verify_batch itself calls
+// (launch_prep_stage), into buffers of the caller: pts 2 n rows of 128 bytes (R at i, A at n + i;
+// the A rows are not written when A's term is summed per key: a_rows = 0), scal n rows of 48
+// bytes, bsum BATCH_MAX_GROUPS x 12 64-bit column sums. Nothing after the preparation runs.
+struct BatchPrepInfo {
+  uint32_t groups, group_sigs, a_rows;
+};
+hipError_t launch_batch_prep(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk,
+                             const uint32_t* key_idx, uint32_t n, uint32_t groups, const uint32_t key[10], void* pts,
+                             void* scal, void* bsum, uint8_t* status, hipStream_t s, const void* comb_a,
+                             const uint8_t* key_ok, uint32_t n_keys, const struct ChunkGate* gate,
+                             BatchPrepInfo* info);
 // chain (optional, unchunked calls): k_bv_prep waits for chain[0] (may be null) and chain[1]
 // is recorded after it, so consecutive batches on different streams run their preparations
 // one after another and each overlaps the previous batches' narrow tails (sort, reduce, final)

@@ -309,3 +309,19 @@ def r4_addn(a, b, strict=True):
 
 def r4_sub(a, b, strict=True):
     return r4_carry(_sub_raw(a, b, strict, "r4::sub"), strict)
+
+
+# ---- tables.h: a precomp entry as stored (7 quads, or 8 with the batch path's padding) ----
+def precomp_to_quads(ypx, ymx, xy2d, quads=7):
+    """The 4 * quads words precomp_to_quads writes for the limb vectors (y+x, y-x, 2dxy)."""
+    w = list(ypx) + list(ymx) + list(xy2d)
+    assert len(w) == 27 and quads >= 7
+    return w + [0] * (4 * quads - 27)
+
+
+def quads_to_precomp(words):
+    """The inverse (quads_to_precomp): the stored words of one entry -> the three limb vectors.
+    The words past the 27th are padding and must be zero."""
+    w = [int(x) for x in words]
+    assert len(w) >= 28 and len(w) % 4 == 0 and not any(w[27:]), "not a precomp row"
+    return w[0:9], w[9:18], w[18:27]

@@ -136,6 +136,10 @@ extern "C" {
     pub fn mv_set_stage_timing(ctx: *mut mv_ctx, enable: i32) -> i32;
     pub fn mv_stage_times(ctx: *mut mv_ctx, ms: *mut f64, calls: *mut u64, reset: i32) -> i32;
     pub fn mv_selftest(ctx: *mut mv_ctx, op: i32, input: *const u32, n: u32, out: *mut u32) -> i32;
+    pub fn mv_selftest_batch_prep(ctx: *mut mv_ctx, msg: *const u8, sig: *const u8, pk: *const u8,
+                                  key_idx: *const u32, n: u32, groups: u32, key: *const u8, launch_sigs: u32,
+                                  scal: *mut u32, pts: *mut u32, bsum: *mut u64, status: *mut u8,
+                                  info: *mut u32) -> i32;
     pub fn mv_set_option(ctx: *mut mv_ctx, name: *const c_char, value: i64) -> i32;
     pub fn mv_get_option(ctx: *mut mv_ctx, name: *const c_char, value: *mut i64) -> i32;
 }
