@@ -483,6 +483,22 @@ mv_status mv_selftest_batch_prep(mv_ctx* ctx, const uint8_t* msg, const uint8_t*
                                  const uint32_t* key_idx, uint32_t n, uint32_t groups, const uint8_t* key,
                                  uint32_t launch_sigs, uint32_t* scal, uint32_t* pts, uint64_t* bsum,
                                  uint8_t* status, uint32_t* info);
+/* Test entry: the stages of the batch path between the preparation and the fallback (the sort of
+ * the bucket entries, the bucket sums, the per-key A term, the reduction and k_bv_final,
+ * batch.hip), launched by the helper the production path launches them with, on rows of the
+ * caller's in the layout mv_selftest_batch_prep returns: scal n x 12 words (z < 2^127, z k < 2^253),
+ * pts 2 n x 32 words (R at i, A at n + i), bsum 16 x 12 column sums. groups: the sub-batch count
+ * asked for. key_idx (optional, with n_keys <= 512 keys of the committee set by mv_set_committee):
+ * the per-key form, in which A's term is [sum z k mod l] A_b per key on the committee's tables
+ * and only the n R rows of pts are read. Out (host): win 16 x 16 x 36 words, of which groups x nw
+ * rows are written, row g * nw + w the extended point (X, Y, Z, T in 9 limbs each) of group g's
+ * window w as k_bv_final reads it; asum 16 x 36 words, the groups' per-key A terms (per-key form
+ * only); flags 17 words: 1 if every group's equation held, then one per group; info 3 words:
+ * groups, signatures per group, nw (16, or 8 in the per-key form). The kernel forms follow the
+ * context's options (mv_set_option). No counter, guard or route is touched and no fallback runs. */
+mv_status mv_selftest_batch_msm(mv_ctx* ctx, uint32_t n, uint32_t groups, const uint32_t* scal, const uint32_t* pts,
+                                const uint64_t* bsum, const uint32_t* key_idx, uint32_t n_keys, uint32_t* win,
+                                uint32_t* asum, uint32_t* flags, uint32_t* info);
 
 #ifdef __cplusplus
 }

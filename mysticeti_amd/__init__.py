@@ -55,7 +55,7 @@ BLOCK_STATUS = [
 EXPORTS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_version", "mv_set_committee", "mv_blake2b256",
     "mv_ed25519_verify", "mv_ed25519_sign", "mv_verify_blocks", "mv_dev_ed25519_verify",
-    "mv_dev_ed25519_sign", "mv_selftest", "mv_selftest_batch_prep", "mv_block_preimage", "mv_dev_ed25519_verify_batch", "mv_batch_stats",
+    "mv_dev_ed25519_sign", "mv_selftest", "mv_selftest_batch_prep", "mv_selftest_batch_msm", "mv_block_preimage", "mv_dev_ed25519_verify_batch", "mv_batch_stats",
     "mv_set_stage_timing", "mv_stage_times", "mv_dev_verify_blocks", "mv_batch_counters", "mv_batch_routes", "mv_set_batch_groups",
     "mv_queue_stats", "mv_shard_plan", "mv_crc32", "mv_wal_verify", "mv_wal_layout", "mv_dev_wal_verify",
     "mv_frame_blocks", "mv_frame_messages", "mv_verify_frames", "mv_dev_verify_frames",
@@ -128,6 +128,7 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_ed25519_sign.argtypes = [vp, ctypes.c_int, vp, vp, u32, vp, vp, vp]
     lib.mv_selftest.argtypes = [vp, ctypes.c_int, vp, u32, vp]
     lib.mv_selftest_batch_prep.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp]
+    lib.mv_selftest_batch_msm.argtypes = [vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     lib.mv_block_preimage.argtypes = [vp, u64, vp, u64]
     lib.mv_block_preimage.restype = ctypes.c_int64
     lib.mv_crc32.argtypes = [vp, vp, vp, vp, u32, vp]
@@ -627,6 +628,33 @@ class Engine:
                     "mv_selftest_batch_prep")
         return BatchPrep(scal, pts, bsum, st, int(info[0]), int(info[1]), bool(info[2]))
 
+    def batch_msm(self, scal, pts, bsum, groups: int = 1, key_idx=None, n_keys: int = 0) -> "BatchMsm":
+        """The batch path's stages after the preparation (mv_selftest_batch_msm: sort, buckets,
+        per-key A term, reduction and k_bv_final, launched as a verify call launches them) on rows in
+        BatchPrep's layout: scal (n, 12), pts (2 n, 32) -- (n, 32) will do with key_idx --, bsum
+        (16, 12) uint64. key_idx / n_keys: the per-key form on the committee that is set. Returns a
+        BatchMsm."""
+        scal = np.ascontiguousarray(np.asarray(scal, dtype=np.uint32))
+        n = scal.shape[0]
+        pts = np.ascontiguousarray(np.asarray(pts, dtype=np.uint32))
+        bsum = np.ascontiguousarray(np.asarray(bsum, dtype=np.uint64))
+        ki = np.ascontiguousarray(np.asarray(key_idx, dtype=np.uint32)) if key_idx is not None else None
+        if scal.shape != (n, 12) or pts.shape not in ((2 * n, 32),) + (((n, 32),) if ki is not None else ()):
+            raise ValueError("scal: (n, 12), pts: (2 n, 32)")
+        if bsum.shape != (BATCH_MAX_GROUPS, 12) or (ki is not None and ki.shape != (n,)):
+            raise ValueError("bsum: (16, 12), key_idx: (n,)")
+        win = np.zeros((BATCH_MAX_GROUPS * 16, 36), dtype=np.uint32)
+        asum = np.zeros((BATCH_MAX_GROUPS, 36), dtype=np.uint32)
+        flags = np.zeros(1 + BATCH_MAX_GROUPS, dtype=np.uint32)
+        info = np.zeros(3, dtype=np.uint32)
+        self._check(self.lib.mv_selftest_batch_msm(self.ctx, n, int(groups), _p(scal), _p(pts), _p(bsum), _p(ki),
+                                                   int(n_keys), _p(win), _p(asum), _p(flags), _p(info)),
+                    "mv_selftest_batch_msm")
+        g, nw = int(info[0]), int(info[2])
+        return BatchMsm(win[:g * nw].reshape(g, nw, 36) if g else win[:0].reshape(0, 0, 36),
+                        asum[:g] if ki is not None else None, int(flags[0]), [int(f) for f in flags[1:1 + g]], g,
+                        int(info[1]))
+
 
 def block_preimage(bincode: bytes) -> Optional[bytes]:
     """Host-side pre-image of one bincode StatementBlock (None if it does not deserialize)."""
@@ -698,6 +726,17 @@ class BatchPrep:
     def group_sum(self, g: int) -> int:
         """sum z_i s_i over group g, from its 12 columns (each a sum of 32-bit words)."""
         return sum(int(c) << (32 * k) for k, c in enumerate(self.bsum[g]))
+
+
+class BatchMsm:
+    """Result of Engine.batch_msm (include/mysti_verify.h, mv_selftest_batch_msm). win: (groups, nw,
+    36) uint32, the extended point (X, Y, Z, T, 9 limbs each) of every group's window sum as
+    k_bv_final read it (nw = 16, or 8 in the per-key form); asum: (groups, 36) per-key A terms or
+    None; flag_all and flags[g]: the equation held; groups, group_sigs: the geometry used."""
+
+    def __init__(self, win, asum, flag_all, flags, groups, group_sigs):
+        self.win, self.asum, self.flag_all, self.flags = win, asum, flag_all, flags
+        self.groups, self.group_sigs = groups, group_sigs
 
 
 class WalReplay:

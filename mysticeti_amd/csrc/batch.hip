@@ -1524,20 +1524,29 @@ hipError_t launch_batch_prep(const Knobs& kn, const uint8_t* msg, const uint8_t*
   return hipGetLastError();
 }
 
-hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* key_idx,
-                               uint32_t n, uint32_t groups, const uint32_t key[10], const void* btab,
-                               void* bscratch, void* vscratch, uint8_t* status, hipStream_t s,
-                               uint32_t** flag_out, hipEvent_t* ev, const void* comb_a, const uint8_t* key_ok,
-                               uint32_t n_keys, const void* comb_b, const ChunkGate* gate, const hipEvent_t* chain) {
+namespace {
+// Everything between the preparation and the fallback of a batch of n signatures in groups G, the
+// one place it is launched from: the sort of the bucket entries of scal, the bucket sums of pts,
+// the per-key A term (agg: key_idx, n_keys and the committee's comb tables comb_a; no A entries),
+// the reduction tree and k_bv_final on bsum, all in the batch scratch's layout. launch_verify_batch
+// runs it between launch_prep_stage and launch_verify; launch_batch_msm (the test entry
+// mv_selftest_batch_msm) runs it on scalars, points and column sums of the caller's and reads
+// back what MsmStage names.
+struct MsmStage {
+  const uint4* winV;  // the last reduction level's window sums k_bv_final read: G.count x nw rows
+  const uint4* asum;  // the groups' per-key A terms (agg), else nullptr
+  uint32_t nw;        // windows with bucket entries
+};
+hipError_t launch_msm_stage(const Knobs& kn, const uint32_t* key_idx, uint32_t n, const mv::BvGroups& G, bool agg,
+                            uint32_t n_keys, const void* comb_a, const void* comb_b, void* bscratch, hipStream_t s,
+                            hipEvent_t* ev, MsmStage* out) {
   using namespace mv;
-  // optional stage events (engine stage timing): ev[0] before prep, ev[i + 1] after stage i
+  // optional stage events (engine stage timing): ev[1 + i] after stage i of sort .. final
   auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], s); };
-  if (n == 0) return hipSuccess;
-  const BvGroups G = batch_groups(n, groups);
   const BatchLayout L(n, G.count);
   char* base = static_cast<char*>(bscratch);
-  uint4* pts = (uint4*)(base + L.pts);
-  uint4* scal = (uint4*)(base + L.scal);
+  const uint4* pts = (const uint4*)(base + L.pts);
+  const uint4* scal = (const uint4*)(base + L.scal);
   uint32_t* pcount = (uint32_t*)(base + L.pcount);
   uint32_t* poff = (uint32_t*)(base + L.poff);
   uint32_t* ptot = (uint32_t*)(base + L.ptot);
@@ -1554,17 +1563,8 @@ hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_
   uint4* keyp = (uint4*)(base + L.keyp);
   uint4* asum = (uint4*)(base + L.asum);
   uint32_t* flag = (uint32_t*)(base + L.flag);
-  if (flag_out) *flag_out = flag;
-  hipError_t e;
   const uint32_t nchunk = (n + PART_CHUNK - 1) / PART_CHUNK;
   const uint32_t nparts = G.count * BV_NPG;
-  mark(0);
-  PrepStage ps;
-  e = launch_prep_stage(kn, msg, sig, pk, key_idx, n, G, key, pts, scal, bsum, status, s, comb_a, key_ok, n_keys, gate,
-                        chain, &ps);
-  if (e != hipSuccess) return e;
-  const CommitteeA& ca = ps.ca;
-  const bool agg = ps.agg;
   const uint32_t nw = agg ? BV_NWR : BV_NW;  // windows with bucket entries
   const uint32_t seg = bucket_segment(kn);
   const uint32_t nk = G.count * BV_NKG;
@@ -1645,7 +1645,37 @@ hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_
   hipLaunchKernelGGL(k_bv_final, dim3(1), dim3(128), 0, s, inV, nw, agg ? (const uint4*)asum : nullptr, bsum,
                      G.count, static_cast<const uint4*>(comb_b), flag, kn.final_rows ? 1u : 0u);
   mark(5);
-  e = hipGetLastError();
+  *out = MsmStage{inV, agg ? (const uint4*)asum : nullptr, nw};
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* key_idx,
+                               uint32_t n, uint32_t groups, const uint32_t key[10], const void* btab,
+                               void* bscratch, void* vscratch, uint8_t* status, hipStream_t s,
+                               uint32_t** flag_out, hipEvent_t* ev, const void* comb_a, const uint8_t* key_ok,
+                               uint32_t n_keys, const void* comb_b, const ChunkGate* gate, const hipEvent_t* chain) {
+  using namespace mv;
+  // optional stage events (engine stage timing): ev[0] before prep, ev[i + 1] after stage i
+  auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], s); };
+  if (n == 0) return hipSuccess;
+  const BvGroups G = batch_groups(n, groups);
+  const BatchLayout L(n, G.count);
+  char* base = static_cast<char*>(bscratch);
+  uint4* pts = (uint4*)(base + L.pts);
+  uint4* scal = (uint4*)(base + L.scal);
+  unsigned long long* bsum = (unsigned long long*)(base + L.bsum);
+  uint32_t* flag = (uint32_t*)(base + L.flag);
+  if (flag_out) *flag_out = flag;
+  hipError_t e;
+  mark(0);
+  PrepStage ps;
+  e = launch_prep_stage(kn, msg, sig, pk, key_idx, n, G, key, pts, scal, bsum, status, s, comb_a, key_ok, n_keys, gate,
+                        chain, &ps);
+  if (e != hipSuccess) return e;
+  const CommitteeA& ca = ps.ca;
+  MsmStage ms;
+  e = launch_msm_stage(kn, key_idx, n, G, ps.agg, n_keys, comb_a, comb_b, bscratch, s, ev, &ms);
   if (e != hipSuccess) return e;
   // exact fallback: re-verifies the signatures of every group whose equation failed
   // (R and A as k_bv_prep decoded them: no decompression)
@@ -1653,6 +1683,35 @@ hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_
                     ca.tab && ca.aggregate ? comb_a : nullptr);
   mark(6);
   return e;
+}
+
+hipError_t launch_batch_msm(const Knobs& kn, uint32_t n, uint32_t groups, const void* h_scal, const void* h_pts,
+                            const void* h_bsum, const uint32_t* key_idx, uint32_t n_keys, const void* comb_a,
+                            const void* comb_b, void* bscratch, size_t scratch_bytes, hipStream_t s,
+                            BatchMsmInfo* info) {
+  using namespace mv;
+  if (n == 0) return hipSuccess;
+  const BvGroups G = batch_groups(n, groups);
+  const BatchLayout L(n, G.count);
+  const bool agg = key_idx != nullptr;
+  if (scratch_bytes < L.total || (agg && (!comb_a || n_keys == 0 || n_keys > (uint32_t)BV_MAXKEYS || agg_disabled(kn))))
+    return hipErrorInvalidValue;
+  char* base = static_cast<char*>(bscratch);
+  hipError_t e;
+  // the caller's rows where k_bv_prep would have written them (no A rows in the per-key form)
+  if ((e = hipMemcpyAsync(base + L.scal, h_scal, (size_t)n * SC_QUADS * 16, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return e;
+  if ((e = hipMemcpyAsync(base + L.pts, h_pts, (size_t)(agg ? 1 : 2) * n * PT_QUADS * 16, hipMemcpyHostToDevice, s)) !=
+      hipSuccess)
+    return e;
+  if ((e = hipMemcpyAsync(base + L.bsum, h_bsum, (size_t)BV_MAXG * BSUM_WORDS * 8, hipMemcpyHostToDevice, s)) !=
+      hipSuccess)
+    return e;
+  MsmStage ms;
+  e = launch_msm_stage(kn, key_idx, n, G, agg, n_keys, comb_a, comb_b, bscratch, s, nullptr, &ms);
+  if (e != hipSuccess) return e;
+  *info = BatchMsmInfo{G.count, G.cpg * PART_CHUNK, ms.nw, ms.winV, ms.asum, (const uint32_t*)(base + L.flag)};
+  return hipSuccess;
 }
 
 }  // namespace mvk

@@ -1276,4 +1276,50 @@ mv_status mv_selftest_batch_prep(mv_ctx* ctx, const uint8_t* msg, const uint8_t*
   return MV_OK;
 }
 
+mv_status mv_selftest_batch_msm(mv_ctx* ctx, uint32_t n, uint32_t groups, const uint32_t* scal, const uint32_t* pts,
+                                const uint64_t* bsum, const uint32_t* key_idx, uint32_t n_keys, uint32_t* win,
+                                uint32_t* asum, uint32_t* flags, uint32_t* info) {
+  if (!ctx || !bsum || !win || !asum || !flags || !info || (n && (!scal || !pts)))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad batch msm args");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device& dev = ctx->devs[0];
+  if (key_idx) {
+    if (!ctx->has_committee || !dev.committee_loaded || (ctx->flags & MV_FLAG_NO_COMB))
+      return set_err(ctx, MV_E_NO_COMMITTEE, "key_idx given but no committee with comb tables set");
+    if (n_keys == 0 || n_keys > ctx->committee.size() || n_keys > 512 || ctx->kn.no_key_agg)
+      return set_err(ctx, MV_E_INVALID_ARG, "per-key form: 1..512 keys of the committee, MV_NO_KEY_AGG off");
+    for (uint32_t i = 0; i < n; i++)
+      if (key_idx[i] >= n_keys) return set_err(ctx, MV_E_INVALID_ARG, "key_idx out of range");
+  }
+  // the bucket keys of a larger scalar would leave the key space (k_bv_prep never writes one)
+  for (uint32_t i = 0; i < n; i++)
+    if ((scal[12 * (size_t)i + 3] >> 31) || (scal[12 * (size_t)i + 11] >> 29))
+      return set_err(ctx, MV_E_INVALID_ARG, "scal: z < 2^127 and z k < 2^253");
+  info[0] = info[1] = info[2] = 0;
+  if (n == 0) return MV_OK;
+  HIPCHK(ctx, hipSetDevice(dev.id));
+  // buffers of this call alone (released on return), as mv_selftest_batch_prep's
+  const uint32_t gs = mvk::batch_group_size(n, groups), ng = (n + gs - 1) / gs;
+  const size_t bytes = mvk::batch_scratch_bytes(n, ng);
+  mvr::DevBuf d_scr, d_ki;
+  HIPCHK(ctx, d_scr.ensure(bytes));
+  hipStream_t s = dev.stream;
+  if (key_idx) {
+    HIPCHK(ctx, d_ki.ensure(4 * (size_t)n));
+    HIPCHK(ctx, hipMemcpyAsync(d_ki.p, key_idx, 4 * (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  mvk::BatchMsmInfo mi{};
+  HIPCHK(ctx, mvk::launch_batch_msm(ctx->kn, n, groups, scal, pts, bsum, key_idx ? d_ki.as<uint32_t>() : nullptr, n_keys,
+                                    key_idx ? dev.tab.combA.p : nullptr, dev.tab.combB.p, d_scr.p, bytes, s, &mi));
+  constexpr size_t kP3Row = 144;
+  HIPCHK(ctx, hipMemcpyAsync(win, mi.win, kP3Row * mi.groups * mi.nw, hipMemcpyDeviceToHost, s));
+  if (mi.asum) HIPCHK(ctx, hipMemcpyAsync(asum, mi.asum, kP3Row * mi.groups, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipMemcpyAsync(flags, mi.flag, 4 * (size_t)(1 + mi.groups), hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  info[0] = mi.groups;
+  info[1] = mi.group_sigs;
+  info[2] = mi.nw;
+  return MV_OK;
+}
+
 }  // extern "C"

@@ -129,6 +129,26 @@ hipError_t launch_batch_prep(const Knobs& kn, const uint8_t* msg, const uint8_t*
                              void* scal, void* bsum, uint8_t* status, hipStream_t s, const void* comb_a,
                              const uint8_t* key_ok, uint32_t n_keys, const struct ChunkGate* gate,
                              BatchPrepInfo* info);
+// The stages after the preparation alone (the test entry mv_selftest_batch_msm): sort, buckets,
+// per-key A term, reduction and k_bv_final, by the helper launch_verify_batch itself calls
+// (launch_msm_stage), on the caller's host rows: h_scal n rows of 48 bytes (z < 2^127 and z k <
+// 2^253: the caller checks, a larger scalar's bucket key would leave the key space), h_pts 2 n
+// rows of 128 bytes (n rows in the per-key form), h_bsum BATCH_MAX_GROUPS x 12 column sums. They
+// are copied into bscratch (scratch_bytes >= batch_scratch_bytes(n, the group count used)) where
+// k_bv_prep writes them. key_idx (device, with comb_a and n_keys <= 512): the per-key form.
+// info: the geometry and the device addresses (inside bscratch) of the window sums k_bv_final
+// read (groups x nw rows of 9 quads), the groups' per-key A terms (per-key form, else null) and
+// the 1 + groups flag words. No fallback runs.
+struct BatchMsmInfo {
+  uint32_t groups, group_sigs, nw;
+  const uint4* win;
+  const uint4* asum;
+  const uint32_t* flag;
+};
+hipError_t launch_batch_msm(const Knobs& kn, uint32_t n, uint32_t groups, const void* h_scal, const void* h_pts,
+                            const void* h_bsum, const uint32_t* key_idx, uint32_t n_keys, const void* comb_a,
+                            const void* comb_b, void* bscratch, size_t scratch_bytes, hipStream_t s,
+                            BatchMsmInfo* info);
 // chain (optional, unchunked calls): k_bv_prep waits for chain[0] (may be null) and chain[1]
 // is recorded after it, so consecutive batches on different streams run their preparations
 // one after another and each overlaps the previous batches' narrow tails (sort, reduce, final)
