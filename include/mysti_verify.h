@@ -499,6 +499,14 @@ mv_status mv_selftest_batch_prep(mv_ctx* ctx, const uint8_t* msg, const uint8_t*
 mv_status mv_selftest_batch_msm(mv_ctx* ctx, uint32_t n, uint32_t groups, const uint32_t* scal, const uint32_t* pts,
                                 const uint64_t* bsum, const uint32_t* key_idx, uint32_t n_keys, uint32_t* win,
                                 uint32_t* asum, uint32_t* flags, uint32_t* info);
+/* Test entry: reads one radix-256 comb table (comb.h) back from device 0 as it stands: the base
+ * point's (key < 0, built by mv_create) or committee key `key`'s (built by mv_set_committee; it
+ * holds the multiples of -A). out (host): 32 rows x 129 entries x 32 words (528 KB), entry
+ * C[i][j] = [j 256^i]P at words 32 (129 i + j): y+x in words 0..8 (29-bit limbs), y-x in 9..17,
+ * 2dxy in 18..26, all canonical, words 27..31 zero. A plain copy after a stream drain: no kernel
+ * runs. MV_E_NO_COMMITTEE without a committee, MV_E_INVALID_ARG for a key outside it. The table of
+ * a key that does not decode (key_ok 0) is unspecified. */
+mv_status mv_selftest_comb_table(mv_ctx* ctx, int key, uint32_t* out);
 
 #ifdef __cplusplus
 }

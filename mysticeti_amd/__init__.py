@@ -55,7 +55,7 @@ BLOCK_STATUS = [
 EXPORTS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_version", "mv_set_committee", "mv_blake2b256",
     "mv_ed25519_verify", "mv_ed25519_sign", "mv_verify_blocks", "mv_dev_ed25519_verify",
-    "mv_dev_ed25519_sign", "mv_selftest", "mv_selftest_batch_prep", "mv_selftest_batch_msm", "mv_block_preimage", "mv_dev_ed25519_verify_batch", "mv_batch_stats",
+    "mv_dev_ed25519_sign", "mv_selftest", "mv_selftest_batch_prep", "mv_selftest_batch_msm", "mv_selftest_comb_table", "mv_block_preimage", "mv_dev_ed25519_verify_batch", "mv_batch_stats",
     "mv_set_stage_timing", "mv_stage_times", "mv_dev_verify_blocks", "mv_batch_counters", "mv_batch_routes", "mv_set_batch_groups",
     "mv_queue_stats", "mv_shard_plan", "mv_crc32", "mv_wal_verify", "mv_wal_layout", "mv_dev_wal_verify",
     "mv_frame_blocks", "mv_frame_messages", "mv_verify_frames", "mv_dev_verify_frames",
@@ -78,6 +78,7 @@ FLAG_NO_BATCH, FLAG_NO_COMB, FLAG_HOST_PARSE, FLAG_NO_ONLINE = 1, 2, 4, 8
 BATCH_MIN = 4096
 SELFTEST_WIDE_OP = 64  # mv_selftest ops from here on use 64-word rows
 BATCH_MAX_GROUPS = 16  # sub-batch equations per batch at most
+COMB_ROWS, COMB_ENTRIES = 32, 129  # a comb table (csrc/comb.h): radix-256 digit positions, |digit| 0..128
 BATCH_PREP_UNWRITTEN = 0xA5A5A5A5  # Engine.batch_prep: the words of point rows that were not read back
 
 
@@ -129,6 +130,7 @@ def load_library(path: str = LIB_PATH):
     lib.mv_selftest.argtypes = [vp, ctypes.c_int, vp, u32, vp]
     lib.mv_selftest_batch_prep.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     lib.mv_selftest_batch_msm.argtypes = [vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    lib.mv_selftest_comb_table.argtypes = [vp, ctypes.c_int, vp]
     lib.mv_block_preimage.argtypes = [vp, u64, vp, u64]
     lib.mv_block_preimage.restype = ctypes.c_int64
     lib.mv_crc32.argtypes = [vp, vp, vp, vp, u32, vp]
@@ -654,6 +656,16 @@ class Engine:
         return BatchMsm(win[:g * nw].reshape(g, nw, 36) if g else win[:0].reshape(0, 0, 36),
                         asum[:g] if ki is not None else None, int(flags[0]), [int(f) for f in flags[1:1 + g]], g,
                         int(info[1]))
+
+    def comb_table(self, key: Optional[int] = None) -> np.ndarray:
+        """One radix-256 comb table as it stands on device 0 (mv_selftest_comb_table): the base
+        point's (key None) or committee key `key`'s, which holds the multiples of -A. Returns
+        (32, 129, 32) uint32: entry [i][j] = [j 256^i]P as (y+x, y-x, 2dxy) in 9 canonical 29-bit
+        limbs each, then 5 zero words."""
+        out = np.zeros((COMB_ROWS, COMB_ENTRIES, 32), dtype=np.uint32)
+        self._check(self.lib.mv_selftest_comb_table(self.ctx, -1 if key is None else int(key), _p(out)),
+                    "mv_selftest_comb_table")
+        return out
 
 
 def block_preimage(bincode: bytes) -> Optional[bytes]:

@@ -1322,4 +1322,22 @@ mv_status mv_selftest_batch_msm(mv_ctx* ctx, uint32_t n, uint32_t groups, const 
   return MV_OK;
 }
 
+mv_status mv_selftest_comb_table(mv_ctx* ctx, int key, uint32_t* out) {
+  if (!ctx || !out) return set_err(ctx, MV_E_INVALID_ARG, "bad comb table args");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device& dev = ctx->devs[0];
+  const void* src = dev.tab.combB.p;
+  const size_t bytes = mvk::comb_table_bytes(1);
+  if (key >= 0) {
+    if (!ctx->has_committee || !dev.committee_loaded) return set_err(ctx, MV_E_NO_COMMITTEE, "no committee set");
+    if ((size_t)key >= ctx->committee.size()) return set_err(ctx, MV_E_INVALID_ARG, "key outside the committee");
+    src = static_cast<const char*>(dev.tab.combA.p) + bytes * (size_t)key;
+  }
+  HIPCHK(ctx, hipSetDevice(dev.id));
+  HIPCHK(ctx, hipStreamSynchronize(dev.stream));  // the tables are built on this stream
+  HIPCHK(ctx, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, dev.stream));
+  HIPCHK(ctx, hipStreamSynchronize(dev.stream));
+  return MV_OK;
+}
+
 }  // extern "C"

@@ -498,6 +498,15 @@ __global__ void __launch_bounds__(64) k_selftest(int op, const uint32_t* __restr
       for (int i = 8; i < 16; i++) out[16 * (size_t)gid + i] = 0;
       return;
     }
+    case 22: {  // sc_recode256 of a scalar a < 2^253: the packed digit words
+      uint32_t sd[8];
+      sc_recode256(sd, x);
+#pragma unroll
+      for (int i = 0; i < 8; i++) out[16 * (size_t)gid + i] = sd[i];
+#pragma unroll
+      for (int i = 8; i < 16; i++) out[16 * (size_t)gid + i] = 0;
+      return;
+    }
     case 12: {  // fe_canon of raw 255-bit input
       fe_from_words(r, x);
       fe_canon(r, r);

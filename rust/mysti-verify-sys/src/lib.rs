@@ -143,6 +143,7 @@ extern "C" {
     pub fn mv_selftest_batch_msm(ctx: *mut mv_ctx, n: u32, groups: u32, scal: *const u32, pts: *const u32,
                                  bsum: *const u64, key_idx: *const u32, n_keys: u32, win: *mut u32,
                                  asum: *mut u32, flags: *mut u32, info: *mut u32) -> i32;
+    pub fn mv_selftest_comb_table(ctx: *mut mv_ctx, key: i32, out: *mut u32) -> i32;
     pub fn mv_set_option(ctx: *mut mv_ctx, name: *const c_char, value: i64) -> i32;
     pub fn mv_get_option(ctx: *mut mv_ctx, name: *const c_char, value: *mut i64) -> i32;
 }

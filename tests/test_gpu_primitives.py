@@ -230,6 +230,24 @@ def test_second_fixed_base_table(engine):
         assert o[:8].astype("<u4").tobytes() == Z.compress(Z.scalarmult(Z.B_POINT, k * 2**124 % Z.L)), k
 
 
+def test_recode256(engine):
+    """sc_recode256 itself (selftest op 22: the packed digit words) against the model's digits, at
+    the recoding's edges (comb_model.EDGES: no carry, a carry through every byte, every digit -128,
+    a top byte of 0x0f with the carry in) and on random scalars below l."""
+    import comb_model as CM
+
+    r = random.Random(22)
+    names = list(CM.EDGES)
+    ks = [CM.EDGES[k] for k in names] + CM.b_scalars()[::37] + [r.randrange(Z.L) for _ in range(300)]
+    w = np.array([words(k) + [0] * 8 for k in ks], dtype=np.uint32)
+    out = engine.selftest(22, w)
+    for i, (k, o) in enumerate(zip(ks, out)):
+        want = CM.recode256(k)
+        got = [((int(x) >> (8 * b) & 0xFF) ^ 0x80) - 0x80 for x in o[:8] for b in range(4)]
+        assert got == want, (names[i] if i < len(names) else hex(k), got, want)
+        assert not o[8:].any()
+
+
 def test_blake2b_ragged_lengths(engine):
     """Every length 0..700 and some up to 40 KB in one call: the 16 strings of a quad-kernel
     workgroup run different step counts (RFC 7693, checked with hashlib)."""
