@@ -132,8 +132,13 @@ def test_statement_kinds_and_ragged_lengths(engine, host_engine):
         out += [b.bincode() for b in cur]
         prev = cur
     out[3] = out[3][:-5] + bytes([out[3][-5] ^ 1]) + out[3][-4:]
-    st, _, _ = agree(engine, host_engine, out, pks, stakes, 0)
+    st, md, bd = agree(engine, host_engine, out, pks, stakes, 0)
     assert len({int(s) for s in st}) >= 3
+    for i in range(len(out)):
+        ost, omd, obd = O.block_verify(out[i], pks, stakes, 0)
+        assert int(st[i]) == ost, i
+        if ost != O.BLOCK_PARSE_ERROR:
+            assert md[i].tobytes() == omd and bd[i].tobytes() == obd, i
 
 
 def test_every_statement_and_metadata_byte_flipped(engine, host_engine):
