@@ -41,6 +41,13 @@
  *                          NetworkSyncer::process_blocks (net_sync.rs:314-383), whose first
  *                          rejected block ends the message and the connection
  *   mv_frame_messages      the same walk on the host for one stream, without the block verdicts
+ *   mv_index_*             the set of BlockReferences the core answers from: BlockManager::exists_or_pending
+ *                          (block_manager.rs:142-144) and BlockManager::missing (:26, 90-97, 138-140), kept in
+ *                          device memory
+ *   mv_accept_blocks       NetworkSyncer::process_blocks with its `processed` query and skip
+ *                          (net_sync.rs:325-336, core_thread/spawned.rs:140-150) ahead of verify, and after it the
+ *                          include lookups of BlockManager::add_blocks (block_manager.rs:48-136) whose result the
+ *                          syncer requests from peers (net_sync.rs:388-398)
  *
  * Conventions
  *   - The caller owns every buffer passed in and out; they must stay valid for the call.
@@ -72,6 +79,7 @@ typedef int32_t mv_status;
 #define MV_E_NO_DEVICE (-3)
 #define MV_E_NO_COMMITTEE (-4)
 #define MV_E_ALLOC (-5)
+#define MV_E_INDEX_FULL (-6) /* a device-buffer index call: the entries it could add do not fit the reserved index */
 
 /* per-signature verdicts (ed25519_consensus::Error mapping) */
 #define MV_SIG_OK 0
@@ -115,6 +123,21 @@ typedef int32_t mv_status;
 #define MV_MSG_TOO_MANY_REQUESTED 3 /* RequestBlocks above MAXIMUM_BLOCK_REQUEST = 50, net_sync.rs:30, 282-285 */
 #define MV_MSG_NOT_REACHED 4        /* after the message that ended the connection: never processed */
 #define MV_MSG_BAD_SIZE 5           /* frame size above MAX_SIZE = 16 MiB, network.rs:216, 419-422 */
+
+/* states of a BlockReference in the index (mv_index_*). State only rises: the reference never removes
+ * from these sets (unload_below_round only unloads block bodies). */
+#define MV_REF_ABSENT 0 /* no entry */
+#define MV_REF_WANTED 1 /* an accepted block includes it and it has not arrived: a key of block_references_waiting
+                           that is not pending, i.e. BlockManager::missing (block_manager.rs:90-97) */
+#define MV_REF_HAVE 2   /* stored or pending: BlockManager::exists_or_pending (block_manager.rs:142-144) */
+
+/* per-block outcome of mv_accept_blocks */
+#define MV_ACC_REJECTED 0 /* its own MV_BLOCK_* is not OK */
+#define MV_ACC_NEW 1      /* accepted, first with its reference: add_blocks goes on with it */
+#define MV_ACC_KNOWN 2    /* processed before: skipped ahead of verify (net_sync.rs:333-336) */
+#define MV_ACC_DUP 3      /* accepted, but a block of a lower index has the same reference (block_manager.rs:68-72) */
+#define MV_ACC_DROPPED 4  /* OK itself, but a block of its group was rejected: process_blocks returned before
+                             add_blocks (net_sync.rs:352-361) */
 
 /* mv_config.flags */
 #define MV_FLAG_NO_BATCH 1u /* host-buffer verify: never use the batch (random linear combination) path */
@@ -328,7 +351,8 @@ int64_t mv_frame_blocks(const uint8_t* buf, uint64_t len, uint64_t* off, uint64_
  * bad only through a block verdict are still walked and their blocks verified; their rows
  * then become NOT_REACHED.
  * The reference skips blocks it has processed before (net_sync.rs:331-335) ahead of verify; such
- * a block passed the same deterministic check then, so verifying it again changes no verdict.
+ * a block passed the same deterministic check then, so verifying it again changes no verdict
+ * (mv_accept_blocks does skip them, on the index of block references).
  *
  * mv_frame_messages: host only, one stream buf[0, len), stream word 0. The rows carry the
  * statuses the bytes alone decide (OK, frame-level DECODE_ERROR, TOO_MANY_REQUESTED, BAD_SIZE) and
@@ -352,6 +376,64 @@ mv_status mv_verify_frames(mv_ctx* ctx, const uint8_t* buf, const uint64_t* soff
                            uint64_t* consumed /* ns */, uint32_t* drop_msg /* ns */, uint32_t* msgs /* cap_msgs x 8 */,
                            uint64_t cap_msgs, uint64_t* n_msgs, uint64_t* blk_off, uint64_t* blk_len,
                            uint8_t* blk_status /* may be NULL */, uint64_t cap_blocks, uint64_t* n_blocks);
+
+/* ---- the index of block references ----
+ * A set of BlockReferences in device memory (the context's first device), keyed by the 48 bytes of a
+ * reference as six little-endian uint64_t words -- authority, round, the four digest words: words
+ * 3..8 of an mv_wal_replay row -- with a state each (MV_REF_*). It answers what the core answers
+ * around verify: BlockManager::exists_or_pending is "the entry is MV_REF_HAVE" (block_manager.rs:142-144),
+ * BlockManager::missing_blocks is the MV_REF_WANTED entries (:138-140). The genesis references are in
+ * the reference's store from the start (block_store.rs:50-62, types.rs:141-150): the caller inserts
+ * them as MV_REF_HAVE. The index is made on first use; every call takes the context in turn.
+ *
+ * mv_index_reserve: makes the index, or grows it so that `entries` entries fit at a load of at most
+ * 1/2 (the entries are rehashed on the device). Never shrinks. mv_index_clear empties it. */
+mv_status mv_index_reserve(mv_ctx* ctx, uint64_t entries);
+mv_status mv_index_clear(mv_ctx* ctx);
+/* out[0] HAVE entries, out[1] WANTED entries, out[2] the capacity in entries, out[3] rebuilds so far,
+ * out[4] the longest probe (slots examined) of any insert or lookup since the last clear. */
+mv_status mv_index_stats(mv_ctx* ctx, uint64_t* out /* 5 */);
+/* Raises n references to `state` (MV_REF_WANTED or MV_REF_HAVE): absent ones are entered, a WANTED one
+ * becomes HAVE (block_manager.rs:100: an arriving block leaves `missing`), nothing is lowered.
+ * prior[i] (optional) = the state of refs[i] before the call, for every duplicate inside the call
+ * too. Grows the index as needed. */
+mv_status mv_index_insert(mv_ctx* ctx, const uint64_t* refs /* n x 6 */, uint64_t n, uint32_t state,
+                          uint8_t* prior /* n, may be NULL */);
+/* state[i] = MV_REF_* of refs[i] (BlockStore::block_exists || blocks_pending.contains_key for HAVE,
+ * block_manager.rs:68-69). */
+mv_status mv_index_lookup(mv_ctx* ctx, const uint64_t* refs /* n x 6 */, uint64_t n, uint8_t* state /* n */);
+/* The MV_REF_WANTED entries (BlockManager::missing_blocks, block_manager.rs:138-140, which the
+ * synchronizer reads, synchronizer.rs:335), in no particular order: *n = how many there are, the
+ * first `cap` written. */
+mv_status mv_index_wanted(mv_ctx* ctx, uint64_t* refs /* cap x 6 */, uint64_t cap, uint64_t* n);
+/* One accept call: process_blocks (net_sync.rs:314-386) for n received blocks buf[off[i], off[i] +
+ * len[i]) of the messages grp[i] (non-decreasing; NULL: every block is a message of its own), up to
+ * and including what BlockManager::add_blocks reports missing (block_manager.rs:48-136). It restates
+ * one interleaving of the reference's peer tasks: every task's `processed` query ran before any
+ * add_blocks.
+ *  1. A block is KNOWN when its own reference (bytes 0..56, read only when len >= 56, digest length
+ *     word 32) is MV_REF_HAVE in the index as it stood before the call. KNOWN blocks are not
+ *     verified and cannot reject their message, whatever their body holds (net_sync.rs:333-336).
+ *  2. The others go through StatementBlock::verify as in mv_dev_verify_blocks (the comb kernels below
+ *     MV_BATCH_MIN blocks, the walk / batch path from there, chunks of max_batch).
+ *     blk_status[i] = MV_BLOCK_*, MV_BLOCK_OK for KNOWN blocks.
+ *  3. A message is accepted when all its blocks are KNOWN or OK; else its blocks that are not KNOWN
+ *     are MV_ACC_DROPPED (OK) or MV_ACC_REJECTED: process_blocks returns before add_blocks (:352-361).
+ *  4. Of the OK blocks of accepted messages with one reference the lowest index is MV_ACC_NEW, the
+ *     others MV_ACC_DUP (block_manager.rs:68-72). The references of NEW blocks become MV_REF_HAVE.
+ *  5. The includes of NEW blocks (u64 count at byte 56, 56 bytes each from byte 64) that have no
+ *     entry after step 4 become MV_REF_WANTED and are listed in `missing`, each once, ordered by
+ *     (block, include) of their first occurrence: the missing_references of add_blocks (:82-88).
+ *     An include that is a NEW block of the same call is not missing (add_blocks sorts by round, :57;
+ *     this holds across the messages of one call too: their accepted blocks count as one vector).
+ * *n_missing is the total; nothing is written past min(*n_missing, cap_missing) rows. Page-locked
+ * (mv_host_alloc), ordered, disjoint blocks are DMAd in place as mv_verify_blocks does; others are
+ * packed. Grows the index as needed. The suspend / unlock cascade of add_blocks (blocks_pending,
+ * :102-131) and the WAL write stay with the caller. Requires mv_set_committee. */
+mv_status mv_accept_blocks(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off, const uint64_t* len,
+                           const uint64_t* grp /* n, may be NULL */, uint32_t n, uint8_t* blk_status /* n */,
+                           uint8_t* blk_state /* n */, uint64_t* missing /* cap_missing x 6 */, uint64_t cap_missing,
+                           uint64_t* n_missing);
 
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
@@ -415,6 +497,25 @@ mv_status mv_dev_verify_frames(mv_ctx* ctx, int device, const uint8_t* d_buf, ui
                                uint32_t* d_drop_msg, uint32_t* d_msgs, uint64_t cap_msgs, uint64_t* n_msgs,
                                uint64_t* d_blk_off, uint64_t* d_blk_len, uint8_t* d_blk_status, uint64_t cap_blocks,
                                uint64_t* n_blocks, void* stream);
+/* mv_accept_blocks on blocks already in HBM (process_blocks and the lookups of add_blocks as there:
+ * net_sync.rs:314-386, block_manager.rs:48-136): every array is device memory (d_grp may be NULL);
+ * *n_missing is written on the host. d_buf follows mv_dev_verify_blocks: 8-byte aligned, 16 readable
+ * bytes past every block, no overlap. Synchronises `stream` (the counts of blocks to verify and of
+ * includes size the lists). It cannot grow the index: MV_E_INDEX_FULL, decided after verify and
+ * before the first insert with the index unchanged, when the blocks that are not KNOWN plus the
+ * includes of the OK ones may not fit the reserved capacity (mv_index_reserve). */
+mv_status mv_dev_accept_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, uint64_t buf_bytes,
+                               const uint64_t* d_off, const uint64_t* d_len, const uint64_t* d_grp, uint32_t n,
+                               uint8_t* d_blk_status, uint8_t* d_blk_state, uint64_t* d_missing, uint64_t cap_missing,
+                               uint64_t* n_missing, void* stream);
+/* mv_index_insert of n references that lie in device memory at a stride: reference i is the six words
+ * at d_words + i * stride_words (stride_words >= 6). A replay's rows go in straight from HBM
+ * (d_blk_rows + 3, stride 10: BlockStore::open's add_unloaded, block_store.rs:398-404). Enqueue only.
+ * It cannot grow the index: MV_E_INDEX_FULL, with the index unchanged, when n more entries may not
+ * fit. A tag collision (probability 2^-64 per pair at the default MV_INDEX_TAG_BITS) takes more
+ * rounds than the call enqueues ahead; it then surfaces as MV_E_HIP from the next index call. */
+mv_status mv_dev_index_insert(mv_ctx* ctx, int device, const uint64_t* d_words, uint64_t stride_words, uint64_t n,
+                              uint32_t state, void* stream);
 /* crc32fast::hash of n strings of device buffer d_buf at d_off/d_len (device arrays) -> d_out. Enqueue only. */
 mv_status mv_dev_crc32(mv_ctx* ctx, int device, const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len,
                        uint32_t n, uint32_t* d_out, void* stream);
@@ -460,7 +561,8 @@ mv_status mv_stage_times(mv_ctx* ctx, double* ms /* MV_NSTAGES or NULL */, uint6
  * mv_create (MV_PASS_SETS, MV_GUARD_GROUPS, MV_BASE_GROUPS), are MV_E_INVALID_ARG. No switch
  * changes a verdict, digest or crc. mv_get_option also reads "MV_LIVE_RESOURCES", the
  * process-wide count of live device resources (buffers, events, streams, retired blocks);
- * mv_set_option refuses it. */
+ * mv_set_option refuses it. MV_INDEX_TAG_BITS (1..64, default 64) truncates the slot tags of the
+ * index from the next mv_index_reserve or mv_index_clear on (tests make tag collisions common). */
 mv_status mv_set_option(mv_ctx* ctx, const char* name, int64_t value);
 mv_status mv_get_option(mv_ctx* ctx, const char* name, int64_t* value);
 /* Runs field/scalar primitive `op` on n lane inputs (16 words each) -> 16 words each (host buffers).

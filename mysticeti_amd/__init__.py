@@ -25,6 +25,13 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
                            handle_read_stream + the NetworkMessage decode (network.rs:400-457) and
                            process_blocks (net_sync.rs:314-383), for many connections at once
   Engine.dev_verify_frames the same on bytes already in HBM
+  Engine.index_*           the BlockReferences the core answers from, in device memory:
+                           BlockManager::exists_or_pending and ::missing (block_manager.rs:26, 138-144)
+  Engine.accept_blocks     process_blocks with its `processed` skip ahead of verify (net_sync.rs:325-336)
+                           and the include lookups of BlockManager::add_blocks after it
+                           (block_manager.rs:48-136): per-block outcomes and the missing references
+  Engine.dev_accept_blocks, Engine.dev_index_insert
+                           the same on buffers already in HBM (a replay's rows go in at a stride)
   frame_messages           the frame and message walk alone, on the host, for one stream
   crypto.*                 thin reference-named wrappers (BlockDigest, PublicKey, Signer, ...)
 """
@@ -59,6 +66,8 @@ EXPORTS = [
     "mv_set_stage_timing", "mv_stage_times", "mv_dev_verify_blocks", "mv_batch_counters", "mv_batch_routes", "mv_set_batch_groups",
     "mv_queue_stats", "mv_shard_plan", "mv_crc32", "mv_wal_verify", "mv_wal_layout", "mv_dev_wal_verify",
     "mv_frame_blocks", "mv_frame_messages", "mv_verify_frames", "mv_dev_verify_frames",
+    "mv_index_reserve", "mv_index_clear", "mv_index_stats", "mv_index_insert", "mv_index_lookup", "mv_index_wanted",
+    "mv_accept_blocks", "mv_dev_accept_blocks", "mv_dev_index_insert",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
@@ -70,6 +79,11 @@ WAL_ROW_WORDS = 10
 MSG_STATUS = ["OK", "DECODE_ERROR", "BLOCK_REJECTED", "TOO_MANY_REQUESTED", "NOT_REACHED", "BAD_SIZE"]
 MSG_OK, MSG_DECODE_ERROR, MSG_BLOCK_REJECTED, MSG_TOO_MANY_REQUESTED, MSG_NOT_REACHED, MSG_BAD_SIZE = range(6)
 MSG_NONE = 0xFFFFFFFF
+# the index of block references: states of a reference, per-block outcomes of accept_blocks
+REF_ABSENT, REF_WANTED, REF_HAVE = 0, 1, 2
+ACC_STATE = ["REJECTED", "NEW", "KNOWN", "DUP", "DROPPED"]
+ACC_REJECTED, ACC_NEW, ACC_KNOWN, ACC_DUP, ACC_DROPPED = range(5)
+E_INDEX_FULL = -6
 WAL_MAP_BITS, WAL_MAP_BITS_TEST = 24, 16  # wal.rs:95-103
 # batch path stages, the block pipeline's, the WAL replay's (mv_stage_times order, MV_NSTAGES)
 STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "hash", "verify", "verdict", "wal_walk",
@@ -83,7 +97,11 @@ BATCH_PREP_UNWRITTEN = 0xA5A5A5A5  # Engine.batch_prep: the words of point rows 
 
 
 class MvError(RuntimeError):
-    pass
+    """A failed library call; `code` is the MV_E_* status when there is one."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 class _Config(ctypes.Structure):
@@ -149,6 +167,15 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_wal_replay.argtypes = [vp, ctypes.c_int, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp,
                                       vp, vp]
     lib.mv_dev_crc32.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, vp, vp]
+    lib.mv_index_reserve.argtypes = [vp, u64]
+    lib.mv_index_clear.argtypes = [vp]
+    lib.mv_index_stats.argtypes = [vp, vp]
+    lib.mv_index_insert.argtypes = [vp, vp, u64, u32, vp]
+    lib.mv_index_lookup.argtypes = [vp, vp, u64, vp]
+    lib.mv_index_wanted.argtypes = [vp, vp, u64, vp]
+    lib.mv_accept_blocks.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, u64, vp]
+    lib.mv_dev_accept_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp]
+    lib.mv_dev_index_insert.argtypes = [vp, ctypes.c_int, vp, u64, u64, u32, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     lib.mv_host_free.argtypes = [vp, vp]
     lib.mv_host_free.restype = None
@@ -236,7 +263,7 @@ class Engine:
 
     def _check(self, rc: int, what: str):
         if rc != MV_OK:
-            raise MvError(f"{what} failed ({rc}): {self.lib.mv_last_error(self.ctx).decode()}")
+            raise MvError(f"{what} failed ({rc}): {self.lib.mv_last_error(self.ctx).decode()}", rc)
 
     # ---- runtime switches (mv_set_option: the environment is read once, at mv_create) ----
     def set_option(self, name: str, value: int):
@@ -593,6 +620,98 @@ class Engine:
         self._check(self.lib.mv_dev_crc32(self.ctx, device, ptr(d_buf), ptr(d_off), ptr(d_len), n, ptr(d_out),
                                           ctypes.c_void_p(stream_handle or None)), "mv_dev_crc32")
 
+    # ---- the index of block references (block_manager.rs) ----
+    def index_reserve(self, entries: int):
+        """Makes the index, or grows it so that `entries` references fit at a load of at most 1/2."""
+        self._check(self.lib.mv_index_reserve(self.ctx, int(entries)), "mv_index_reserve")
+
+    def index_clear(self):
+        self._check(self.lib.mv_index_clear(self.ctx), "mv_index_clear")
+
+    def index_stats(self) -> "IndexStats":
+        out = np.zeros(5, dtype=np.uint64)
+        self._check(self.lib.mv_index_stats(self.ctx, _p(out)), "mv_index_stats")
+        return IndexStats(*(int(x) for x in out))
+
+    def index_insert(self, refs, state: int = REF_HAVE) -> np.ndarray:
+        """Raises references ((n, 6) uint64 words, or (authority, round, digest) tuples) to `state`;
+        returns the state each had before the call."""
+        r = ref_words(refs)
+        prior = np.zeros(r.shape[0], dtype=np.uint8)
+        self._check(self.lib.mv_index_insert(self.ctx, _p(r), r.shape[0], int(state), _p(prior)), "mv_index_insert")
+        return prior
+
+    def index_lookup(self, refs) -> np.ndarray:
+        """REF_* of every reference: REF_HAVE is BlockManager::exists_or_pending."""
+        r = ref_words(refs)
+        st = np.zeros(r.shape[0], dtype=np.uint8)
+        self._check(self.lib.mv_index_lookup(self.ctx, _p(r), r.shape[0], _p(st)), "mv_index_lookup")
+        return st
+
+    def index_wanted(self, cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+        """The REF_WANTED references (BlockManager::missing_blocks) as (k, 6) uint64 words in no
+        particular order, and their total (k = min(total, cap))."""
+        n = ctypes.c_uint64(0)
+        if cap is None:
+            self._check(self.lib.mv_index_wanted(self.ctx, None, 0, ctypes.byref(n)), "mv_index_wanted")
+            cap = int(n.value)
+        out = np.zeros((max(cap, 1), 6), dtype=np.uint64)
+        self._check(self.lib.mv_index_wanted(self.ctx, _p(out), cap, ctypes.byref(n)), "mv_index_wanted")
+        return out[:min(int(n.value), cap)], int(n.value)
+
+    def accept_blocks(self, blocks: Sequence[bytes], groups=None, cap_missing: Optional[int] = None) -> "Accepted":
+        """One accept call (mv_accept_blocks) over bincode blocks; groups: one non-decreasing word
+        per block naming its message, or None (every block a message of its own)."""
+        buf, offs, lens = _pack(blocks)
+        return self.accept_blocks_packed(buf, offs, lens, groups, cap_missing)
+
+    def accept_blocks_packed(self, buf: np.ndarray, offs, lens, groups=None, cap_missing: Optional[int] = None,
+                             missing_out: Optional[np.ndarray] = None) -> "Accepted":
+        """mv_accept_blocks on blocks buf[offs[i], offs[i] + lens[i]). cap_missing None: room for every
+        include (no list is cut). missing_out: the (cap, 6) uint64 array the call writes into."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        n = offs.shape[0]
+        grp = None if groups is None else np.ascontiguousarray(np.asarray(groups, dtype=np.uint64))
+        if grp is not None and grp.shape != (n,):
+            raise ValueError("groups: one word per block")
+        if cap_missing is None:
+            cap_missing = int(lens.sum()) // 56 + 1  # an include takes 56 bytes
+        miss = missing_out if missing_out is not None else np.zeros((max(cap_missing, 1), 6), dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        state = np.zeros(max(n, 1), dtype=np.uint8)
+        nm = ctypes.c_uint64(0)
+        self._check(self.lib.mv_accept_blocks(self.ctx, _p(buf) if buf.size else None, _p(offs), _p(lens), _p(grp), n,
+                                              _p(st), _p(state), _p(miss), cap_missing, ctypes.byref(nm)),
+                    "mv_accept_blocks")
+        return Accepted(st[:n], state[:n], miss[:min(int(nm.value), cap_missing)], int(nm.value))
+
+    def dev_accept_blocks(self, device: int, d_buf, buf_bytes: int, d_off, d_len, d_grp, d_blk_status, d_blk_state,
+                          d_missing, stream_handle: int = 0) -> int:
+        """mv_dev_accept_blocks on torch device tensors (d_buf uint8, 8-byte aligned with 16 readable
+        bytes past every block; d_off / d_len / d_grp int64, d_grp may be None; d_blk_status /
+        d_blk_state uint8; d_missing (cap, 6) int64 or None). Synchronises the stream; returns the
+        missing total, of which the first d_missing.shape[0] rows are written. Raises MvError with
+        code E_INDEX_FULL when the reserved index has no room (the index is unchanged)."""
+        vp = ctypes.c_void_p
+        nm = ctypes.c_uint64(0)
+        self._check(self.lib.mv_dev_accept_blocks(
+            self.ctx, device, vp(d_buf.data_ptr()), int(buf_bytes), vp(d_off.data_ptr()), vp(d_len.data_ptr()),
+            vp(d_grp.data_ptr()) if d_grp is not None else None, d_off.shape[0], vp(d_blk_status.data_ptr()),
+            vp(d_blk_state.data_ptr()), vp(d_missing.data_ptr()) if d_missing is not None else None,
+            d_missing.shape[0] if d_missing is not None else 0, ctypes.byref(nm), vp(stream_handle or None)),
+            "mv_dev_accept_blocks")
+        return int(nm.value)
+
+    def dev_index_insert(self, device: int, d_words, stride_words: int, n: int, state: int = REF_HAVE,
+                         stream_handle: int = 0, word_offset: int = 0):
+        """mv_dev_index_insert: reference i is the six int64 words of torch device tensor d_words at
+        word_offset + i * stride_words (a replay's rows: word_offset 3, stride 10). Enqueue only."""
+        self._check(self.lib.mv_dev_index_insert(self.ctx, device, ctypes.c_void_p(d_words.data_ptr() + 8 * word_offset),
+                                                 int(stride_words), int(n), int(state),
+                                                 ctypes.c_void_p(stream_handle or None)), "mv_dev_index_insert")
+
     # ---- diagnostics ----
     def selftest(self, op: int, words: np.ndarray) -> np.ndarray:
         """Ops 0..63 take and return 16-word rows; ops >= SELFTEST_WIDE_OP (raw-limb field and point
@@ -666,6 +785,26 @@ class Engine:
         self._check(self.lib.mv_selftest_comb_table(self.ctx, -1 if key is None else int(key), _p(out)),
                     "mv_selftest_comb_table")
         return out
+
+
+def _pack(blocks: Sequence[bytes]):
+    lens = np.array([len(b) for b in blocks], dtype=np.uint64)
+    offs = np.zeros(len(blocks), dtype=np.uint64)
+    if len(blocks) > 1:
+        offs[1:] = np.cumsum(lens)[:-1]
+    return np.frombuffer(b"".join(blocks) + b"\0", dtype=np.uint8), offs, lens
+
+
+def ref_words(refs) -> np.ndarray:
+    """(n, 6) uint64 index keys -- authority, round, the four little-endian digest words -- from
+    such an array or from (authority, round, 32-byte digest) tuples (blocks.genesis_refs)."""
+    if isinstance(refs, np.ndarray):
+        return np.ascontiguousarray(refs, dtype=np.uint64).reshape(-1, 6)
+    out = np.zeros((len(refs), 6), dtype=np.uint64)
+    for i, (a, r, d) in enumerate(refs):
+        out[i, 0], out[i, 1] = a, r
+        out[i, 2:] = np.frombuffer(bytes(d), dtype="<u8")
+    return out
 
 
 def block_preimage(bincode: bytes) -> Optional[bytes]:
@@ -749,6 +888,25 @@ class BatchMsm:
     def __init__(self, win, asum, flag_all, flags, groups, group_sigs):
         self.win, self.asum, self.flag_all, self.flags = win, asum, flag_all, flags
         self.groups, self.group_sigs = groups, group_sigs
+
+
+class IndexStats:
+    """Result of Engine.index_stats (mv_index_stats): HAVE and WANTED entries, the capacity in
+    entries, rebuilds so far, the longest probe since the last clear."""
+
+    def __init__(self, have, wanted, capacity, rebuilds, longest_probe):
+        self.have, self.wanted, self.capacity = have, wanted, capacity
+        self.rebuilds, self.longest_probe = rebuilds, longest_probe
+
+
+class Accepted:
+    """Result of Engine.accept_blocks (include/mysti_verify.h, mv_accept_blocks). blk_status: MV_BLOCK_*
+    per block (BLOCK_OK for blocks skipped as known); blk_state: ACC_* per block; missing: (k, 6)
+    uint64 references seen missing for the first time, in (block, include) order; n_missing: their
+    total (above k when cap_missing cut the list)."""
+
+    def __init__(self, blk_status, blk_state, missing, n_missing):
+        self.blk_status, self.blk_state, self.missing, self.n_missing = blk_status, blk_state, missing, n_missing
 
 
 class WalReplay:

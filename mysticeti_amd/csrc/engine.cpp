@@ -492,6 +492,7 @@ const KnobDef kKnobs[] = {
     {"MV_SCATTER_LDS", &mvk::Knobs::scatter_lds, K_ON, false},
     {"MV_FINE_LDS", &mvk::Knobs::fine_lds, K_ON, false},
     {"MV_REDUCE_ROWS", &mvk::Knobs::reduce_rows, K_INT, false},
+    {"MV_INDEX_TAG_BITS", &mvk::Knobs::index_tag_bits, K_INT, false},
 };
 
 // read-only (mv_get_option): the process-wide count of live device resources (dev_resources.h)
@@ -602,6 +603,8 @@ mv_status mv_set_option(mv_ctx* ctx, const char* name, int64_t value) {
   const KnobDef* d = find_knob(name);
   if (!d) return set_err(ctx, MV_E_INVALID_ARG, std::string("unknown option ") + (name ? name : "(null)"));
   if (d->create_only) return set_err(ctx, MV_E_INVALID_ARG, std::string(name) + " is read at mv_create only");
+  if (d->field == &mvk::Knobs::index_tag_bits && (value < 1 || value > 64))
+    return set_err(ctx, MV_E_INVALID_ARG, std::string(name) + " takes 1..64");
   std::lock_guard<std::mutex> lk(ctx->mu);
   ctx->kn.*d->field = d->kind == K_INT ? value : (value != 0);
   return MV_OK;
@@ -640,6 +643,8 @@ mv_status mv_create(const mv_config* cfg, mv_ctx** out) {
   {
     FILE* f = fopen("/dev/urandom", "rb");
     size_t got = f ? fread(ctx->secret, 1, sizeof(ctx->secret), f) : 0;
+    if (got == sizeof(ctx->secret) && fread(ctx->index_secret, 1, sizeof(ctx->index_secret), f) != sizeof(ctx->index_secret))
+      got = 0;
     if (f) fclose(f);
     if (got != sizeof(ctx->secret)) {
       delete ctx;
@@ -778,11 +783,12 @@ void mv_destroy(mv_ctx* ctx) {
     watch.phase("retired buffers");
     reap_retired(dev.id);
     // one release per group, members in declaration order (the device is idle: no order matters)
-    watch.phase("frees: tables, host-call, WAL and frame buffers");
+    watch.phase("frees: tables, host-call, WAL, frame and index buffers");
     mvr::reset(dev.tab);
     mvr::reset(dev.hc);
     mvr::reset(dev.wal);
     mvr::reset(dev.frm);
+    mvr::reset(dev.index);
     watch.phase("frees: batch and single path");
     mvr::reset(dev.batch);
     mvr::reset(dev.single);

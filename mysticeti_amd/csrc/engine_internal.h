@@ -1,6 +1,7 @@
 // What the engine's source files share (host only): the per-device state and the context, the
 // error plumbing, the sharding helpers, and the declarations of the functions that cross files
-// (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp).
+// (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp,
+// engine_index.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -164,6 +165,24 @@ struct Device {
     DevBuf s, f, o, in, tab;
   } frm;
 
+  // the index of block references (index.hip, engine_index.cpp), made on first use: the table
+  // and its control words, and the scratch of insert, lookup, list and accept calls
+  struct Index {
+    DevBuf tab, ctl;
+    DevBuf item, keys, out, wg;  // per-item records, staged keys / sources, results, per-workgroup scans
+    DevBuf acc, accv, in, tab_in, miss;  // mv_accept_blocks: per-block arrays, the verify list, bytes, off | len | grp, the list
+    HostBuf h_ctl;               // the control words read back
+    uint64_t slots = 0;          // a power of two, 0: no table
+    uint64_t used = 0;           // entries: exact after every call that synchronises, else an upper bound
+    bool used_exact = true;
+    // recorded behind every mv_dev_index_insert (which only enqueues, maybe on a caller's stream):
+    // the next index call's stream waits for it, and it guards the per-item records when they grow
+    mvr::Event ahead;
+    bool ahead_set = false;
+    uint64_t rebuilds = 0;
+    uint32_t tag_bits = 64;      // of the table in force
+  } index;
+
   // the resident online service (k_online) of this device, made on first use
   std::shared_ptr<OnlineSvc> online;
 };
@@ -183,6 +202,7 @@ struct mv_ctx {
   uint32_t max_batch = 1u << 20;
   uint32_t flags = 0;
   uint32_t secret[8] = {0};         // batch-path z_i PRF key (from /dev/urandom)
+  uint64_t index_secret[2] = {0};   // the index's hash key (index.hip), drawn with it
   std::atomic<uint64_t> calls{0};   // batch calls, the PRF's per-call input
   std::atomic<uint64_t> batches{0}, fallbacks{0}, groups_run{0}, groups_failed{0};
   // sub-batch equations per batch: groups_fixed != 0 forces that many; 0 = adaptive:

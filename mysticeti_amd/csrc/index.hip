@@ -1,0 +1,693 @@
+// The device-resident index of block references (include/mysti_verify.h: mv_index_*,
+// mv_accept_blocks): a set of BlockReferences with a state each -- MV_REF_HAVE, what
+// BlockManager::exists_or_pending answers (block_manager.rs:142-144), or MV_REF_WANTED, a key of
+// block_references_waiting that is not pending (BlockManager::missing, :90-97) -- and the kernels
+// of one accept call around the block pipeline (process_blocks' skip, net_sync.rs:325-336, and the
+// include lookups of add_blocks, block_manager.rs:62-98). Where references lie in a block:
+// block_ref.h.
+//
+// Table: open addressing, linear probing, 64-byte slots of eight u64 words
+//   [0] tag    0 = empty, else the (truncated) second hash of the key, never 0
+//   [1] meta   low half: the state (0 until the slot is filled); high half: the owner word
+//   [2..7]     the key: authority, round, four digest words
+// Probe start and tag are the two halves of SipHash-2-4-128 of the six key words under the
+// context's 128-bit secret: the digests of includes are bytes a peer chooses. No result rests on
+// a tag: a match is a match only after all six words compare equal.
+//
+// Memory model. Inside one launch lanes talk only through agent-scope atomic read-modify-writes
+// on single words: CAS on the tag, max on the owner word (which holds ~item, so the lowest item
+// wins), max on the state. No lane waits for another, and no kernel compares against key bytes
+// that were stored in the same launch: a slot whose state is 0 was claimed in this launch, and
+// its key is read only by a later kernel. One insert round is three kernels on one stream:
+//   k_ix_claim    probe; a slot filled before this launch (state != 0) is compared in full; the
+//                 first empty slot is claimed by CAS; a lane that stops at a slot (claimed now, or
+//                 found and to be raised) puts its item into the owner word
+//   k_ix_fill     the owner of a claimed slot writes key and state; the owner of a found slot
+//                 raises its state; the counters of HAVE and WANTED entries
+//   k_ix_settle   a lane that stopped at a slot claimed in this round without owning it compares
+//                 in full: equal, it is a duplicate of the owner; different (same tag, other key)
+//                 it is marked for another round, which probes on past that slot. Owners clear
+//                 the owner word.
+// The host runs rounds while the retry counter is not 0 (64-bit tags: never; MV_INDEX_TAG_BITS=2:
+// all the time). All items with one key stop at the same slot in a round (tags are set once and
+// never cleared), so they share their fate, and the owner among them is the lowest item.
+// Every probe loop is bounded by the table size; a probe that runs out sets the error word.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/mysti_verify.h"
+#include "block_ref.h"
+#include "kernels.h"
+
+namespace mv {
+namespace ix {
+
+using mvk::IndexKeys;
+using mvk::IndexTable;
+typedef unsigned long long u64;
+
+constexpr int WG = 256;
+constexpr int SLOT_WORDS = 8;
+
+// an item's record: slot index | prior state << 40 | code << 44 | FRESH
+constexpr u64 SLOT_MASK = (1ull << 40) - 1;
+constexpr int PRIOR_SHIFT = 40, CODE_SHIFT = 44;
+constexpr u64 FRESH = 1ull << 48;  // an owner whose slot's owner word is still set
+enum Code : u64 {
+  C_NONE = 0,     // not an item (no source)
+  C_FOUND = 1,    // matched a slot filled earlier whose state is to be raised
+  C_CLAIMED = 2,  // stopped at a slot claimed in this round
+  C_NEW = 3,      // owner: created the entry
+  C_RAISED = 4,   // owner: raised the entry
+  C_DUP = 5,      // same key as an owner of this call
+  C_NOOP = 6,     // the entry was there with a state at least as high
+  C_RETRY = 7,    // same tag, other key: probes on in the next round
+  C_FAIL = 8,     // the probe ran through the whole table
+};
+
+__device__ inline u64 pack(u64 slot, uint32_t prior, u64 code) {
+  return slot | ((u64)prior << PRIOR_SHIFT) | (code << CODE_SHIFT);
+}
+__device__ inline u64 code_of(u64 it) { return (it >> CODE_SHIFT) & 15; }
+__device__ inline uint32_t prior_of(u64 it) { return (uint32_t)(it >> PRIOR_SHIFT) & 3; }
+
+__device__ inline uint64_t ld64(const uint8_t* p) {
+  uint64_t v;
+  __builtin_memcpy(&v, p, 8);
+  return v;
+}
+
+#define MV_SIPROUND                                  \
+  do {                                               \
+    v0 += v1, v1 = (v1 << 13) | (v1 >> 51), v1 ^= v0; \
+    v0 = (v0 << 32) | (v0 >> 32);                    \
+    v2 += v3, v3 = (v3 << 16) | (v3 >> 48), v3 ^= v2; \
+    v0 += v3, v3 = (v3 << 21) | (v3 >> 43), v3 ^= v0; \
+    v2 += v1, v1 = (v1 << 17) | (v1 >> 47), v1 ^= v2; \
+    v2 = (v2 << 32) | (v2 >> 32);                    \
+  } while (0)
+
+// SipHash-2-4 with 128-bit output over the 48 key bytes: *start = first half, the tag from the second
+__device__ inline void hash_key(const IndexTable& t, const uint64_t k[6], uint64_t* start, uint64_t* tag) {
+  uint64_t v0 = t.k0 ^ 0x736f6d6570736575ull, v1 = t.k1 ^ 0x646f72616e646f6dull;
+  uint64_t v2 = t.k0 ^ 0x6c7967656e657261ull, v3 = t.k1 ^ 0x7465646279746573ull;
+  v1 ^= 0xee;
+#pragma unroll
+  for (int w = 0; w < 6; w++) {
+    v3 ^= k[w];
+    MV_SIPROUND;
+    MV_SIPROUND;
+    v0 ^= k[w];
+  }
+  const uint64_t b = 48ull << 56;
+  v3 ^= b;
+  MV_SIPROUND;
+  MV_SIPROUND;
+  v0 ^= b;
+  v2 ^= 0xee;
+  for (int r = 0; r < 4; r++) MV_SIPROUND;
+  *start = (v0 ^ v1 ^ v2 ^ v3) & t.mask;
+  v1 ^= 0xdd;
+  for (int r = 0; r < 4; r++) MV_SIPROUND;
+  uint64_t g = v0 ^ v1 ^ v2 ^ v3;
+  if (t.tag_bits < 64) g &= (1ull << t.tag_bits) - 1;
+  *tag = g ? g : 1;
+}
+
+__device__ inline const uint8_t* key_ptr(const IndexKeys& ks, uint64_t i) {
+  return ks.base + (ks.off ? ks.off[i] : i * ks.stride);
+}
+__device__ inline void load_key(const IndexKeys& ks, uint64_t i, uint64_t k[6]) {
+  const uint8_t* p = key_ptr(ks, i);
+#pragma unroll
+  for (int w = 0; w < 6; w++) k[w] = ld64(p + (ks.ref ? br::key_word_off(w) : 8 * (uint64_t)w));
+}
+__device__ inline bool has_src(const IndexKeys& ks, uint64_t i) { return !ks.off || ks.off[i] != mvk::IX_NO_SRC; }
+
+// plain loads: the slot was filled by an earlier kernel
+__device__ inline bool key_eq(const u64* slot, const uint64_t k[6]) {
+  bool eq = true;
+#pragma unroll
+  for (int w = 0; w < 6; w++) eq &= slot[2 + w] == k[w];
+  return eq;
+}
+__device__ inline uint32_t* meta_of(u64* slot) { return reinterpret_cast<uint32_t*>(slot + 1); }
+
+// the wave's maximum of v into *dst (every lane of the wave calls)
+__device__ inline void wave_max_to(u64* dst, uint32_t v) {
+  for (int d = 32; d; d >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)v, d);
+    v = o > v ? o : v;
+  }
+  if ((threadIdx.x & 63) == 0 && v) atomicMax(dst, (u64)v);
+}
+// the wave's count of `flag` added to *dst (every lane of the wave calls)
+__device__ inline void wave_count_to(u64* dst, bool flag, bool negative = false) {
+  const u64 m = __ballot(flag);
+  if ((threadIdx.x & 63) == 0 && m) {
+    const u64 c = (u64)__popcll(m);
+    atomicAdd(dst, negative ? (u64)0 - c : c);
+  }
+}
+
+// Exclusive prefix of v over the workgroup and the workgroup's total (every lane calls).
+__device__ inline uint64_t wg_excl(uint64_t v, uint64_t* total) {
+  __shared__ uint64_t wsum[WG / 64];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x / 64;
+  uint64_t inc = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), d);
+    if (lane >= (uint32_t)d) inc += ((uint64_t)hi << 32) | lo;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  uint64_t base = 0, tot = 0;
+  for (uint32_t w = 0; w < WG / 64; w++) {
+    if (w < wave) base += wsum[w];
+    tot += wsum[w];
+  }
+  __syncthreads();
+  *total = tot;
+  return base + inc - v;
+}
+
+// wgbase[g] = the counts of the workgroups before g; *total = all of them (k_replay_scan's shape)
+__global__ void __launch_bounds__(1024) k_ix_scan(const uint64_t* __restrict__ wgcount, uint64_t nwg,
+                                                  uint64_t* __restrict__ wgbase, uint64_t* __restrict__ total) {
+  __shared__ uint64_t part[1024];
+  const uint64_t per = (nwg + 1023) / 1024;
+  const uint64_t lo = per * threadIdx.x < nwg ? per * threadIdx.x : nwg;
+  const uint64_t hi = lo + per < nwg ? lo + per : nwg;
+  uint64_t sum = 0;
+  for (uint64_t g = lo; g < hi; g++) sum += wgcount[g];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const uint64_t v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
+    __syncthreads();
+    part[threadIdx.x] += v;
+    __syncthreads();
+  }
+  uint64_t acc = part[threadIdx.x] - sum;
+  for (uint64_t g = lo; g < hi; g++) {
+    wgbase[g] = acc;
+    acc += wgcount[g];
+  }
+  if (threadIdx.x == 1023) *total = part[1023];
+}
+
+// ---------------------------------------------------------------- insert rounds
+__global__ void __launch_bounds__(WG) k_ix_claim(IndexTable t, IndexKeys ks, uint64_t n, u64* __restrict__ item,
+                                                 uint32_t newstate, int round, u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool act = i < n;
+  if (act && round == 0) {
+    act = has_src(ks, i);
+    if (!act) item[i] = pack(0, 0, C_NONE);
+  } else if (act) {
+    act = code_of(item[i]) == C_RETRY;
+  }
+  uint32_t probe = 0;
+  bool fail = false;
+  if (act) {
+    uint64_t k[6], start, tag;
+    load_key(ks, i, k);
+    hash_key(t, k, &start, &tag);
+    uint64_t p = round ? ((item[i] & SLOT_MASK) + 1) & t.mask : start;
+    uint64_t dist = (p - start) & t.mask;  // slots already passed in earlier rounds
+    const uint32_t me = ~(uint32_t)i;
+    u64 res = pack(0, 0, C_FAIL);
+    for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
+      u64* slot = t.slots + SLOT_WORDS * p;
+      const u64 old = atomicCAS(slot, 0ull, (u64)tag);
+      if (old == 0) {
+        atomicMax(meta_of(slot) + 1, me);
+        res = pack(p, 0, C_CLAIMED);
+        break;
+      }
+      if (old != tag) continue;
+      const uint32_t st = __hip_atomic_load(meta_of(slot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (st == 0) {  // claimed in this launch: its key is not there yet
+        atomicMax(meta_of(slot) + 1, me);
+        res = pack(p, 0, C_CLAIMED);
+        break;
+      }
+      if (!key_eq(slot, k)) continue;
+      if (st >= newstate) {
+        res = pack(p, st, C_NOOP);
+      } else {
+        atomicMax(meta_of(slot) + 1, me);
+        res = pack(p, st, C_FOUND);
+      }
+      break;
+    }
+    probe = (uint32_t)(dist < 0xffffffffull ? dist + 1 : 0xffffffffull);
+    fail = code_of(res) == C_FAIL;
+    item[i] = res;
+  }
+  wave_max_to(ctl + mvk::IX_CTL_MAXPROBE, probe);
+  wave_count_to(ctl + mvk::IX_CTL_ERR, fail);
+}
+
+__global__ void __launch_bounds__(WG) k_ix_fill(IndexTable t, IndexKeys ks, uint64_t n, u64* __restrict__ item,
+                                                uint32_t newstate, u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool created = false, raised = false;
+  if (i < n) {
+    const u64 it = item[i], c = code_of(it);
+    if (c == C_CLAIMED || c == C_FOUND) {
+      const uint64_t p = it & SLOT_MASK;
+      u64* slot = t.slots + SLOT_WORDS * p;
+      uint32_t* meta = meta_of(slot);
+      const bool owner = meta[1] == ~(uint32_t)i;  // (set by k_ix_claim's atomics, an earlier kernel)
+      if (c == C_CLAIMED && owner) {
+        uint64_t k[6];
+        load_key(ks, i, k);
+#pragma unroll
+        for (int w = 0; w < 6; w++) slot[2 + w] = k[w];
+        atomicMax(meta, newstate);
+        created = true;
+        item[i] = pack(p, 0, C_NEW) | FRESH;
+      } else if (c == C_FOUND) {
+        if (owner) {
+          atomicMax(meta, newstate);
+          raised = true;
+          item[i] = pack(p, prior_of(it), C_RAISED) | FRESH;
+        } else {
+          item[i] = pack(p, prior_of(it), C_DUP);
+        }
+      }
+    }
+  }
+  // the only raise is WANTED -> HAVE
+  if (newstate == MV_REF_HAVE) {
+    wave_count_to(ctl + mvk::IX_CTL_HAVE, created || raised);
+    wave_count_to(ctl + mvk::IX_CTL_WANTED, raised, true);
+  } else {
+    wave_count_to(ctl + mvk::IX_CTL_WANTED, created);
+  }
+}
+
+__global__ void __launch_bounds__(WG) k_ix_settle(IndexTable t, IndexKeys ks, uint64_t n, u64* __restrict__ item,
+                                                  u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool retry = false;
+  if (i < n) {
+    const u64 it = item[i];
+    const uint64_t p = it & SLOT_MASK;
+    u64* slot = t.slots + SLOT_WORDS * p;
+    if (code_of(it) == C_CLAIMED) {  // not the owner: the owner's key is there since k_ix_fill
+      uint64_t k[6];
+      load_key(ks, i, k);
+      retry = !key_eq(slot, k);
+      item[i] = pack(p, 0, retry ? C_RETRY : C_DUP);
+    } else if (it & FRESH) {
+      meta_of(slot)[1] = 0;
+      item[i] = it & ~FRESH;
+    }
+  }
+  wave_count_to(ctl + mvk::IX_CTL_RETRY, retry);
+}
+
+// after the last round a call enqueued ahead: items still left over are given up (the error word)
+__global__ void k_ix_giveup(u64* __restrict__ ctl) {
+  if (threadIdx.x || blockIdx.x) return;
+  if (ctl[mvk::IX_CTL_RETRY]) atomicAdd(ctl + mvk::IX_CTL_ERR, ctl[mvk::IX_CTL_RETRY]);
+}
+
+__global__ void __launch_bounds__(WG) k_ix_prior(const u64* __restrict__ item, uint64_t n, uint8_t* __restrict__ prior) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (i < n) prior[i] = (uint8_t)prior_of(item[i]);
+}
+
+// Read-only probe: the state of key k, MV_REF_ABSENT without an entry. Nothing writes the table
+// in a launch that calls it. *probe = slots examined.
+__device__ inline uint32_t lookup(const IndexTable& t, const uint64_t k[6], uint32_t* probe, bool* fail) {
+  uint64_t start, tag;
+  hash_key(t, k, &start, &tag);
+  uint64_t p = start, dist = 0;
+  uint32_t st = MV_REF_ABSENT;
+  bool ended = false;
+  for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
+    const u64* slot = t.slots + SLOT_WORDS * p;
+    const u64 g = slot[0];
+    if (g == 0) {
+      ended = true;
+      break;
+    }
+    if (g == tag && key_eq(slot, k)) {
+      st = (uint32_t)slot[1];
+      ended = true;
+      break;
+    }
+  }
+  *probe = (uint32_t)(dist < 0xffffffffull ? dist + 1 : 0xffffffffull);
+  *fail = !ended;
+  return st;
+}
+
+__global__ void __launch_bounds__(WG) k_ix_lookup(IndexTable t, IndexKeys ks, uint64_t n, uint8_t* __restrict__ out,
+                                                  u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint32_t probe = 0;
+  bool fail = false;
+  if (i < n) {
+    uint32_t st = MV_REF_ABSENT;
+    if (t.slots && has_src(ks, i)) {
+      uint64_t k[6];
+      load_key(ks, i, k);
+      st = lookup(t, k, &probe, &fail);
+    }
+    out[i] = (uint8_t)st;
+  }
+  wave_max_to(ctl + mvk::IX_CTL_MAXPROBE, probe);
+  wave_count_to(ctl + mvk::IX_CTL_ERR, fail);
+}
+
+// One lane per slot of the old table: its entry into the new one. The keys are distinct, so a
+// lane claims the first empty slot and never compares (no key of this launch is read).
+__global__ void __launch_bounds__(WG) k_ix_rebuild(const u64* __restrict__ old, uint64_t old_slots, IndexTable t,
+                                                   u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint32_t probe = 0;
+  bool fail = false;
+  if (i < old_slots) {
+    const u64* src = old + SLOT_WORDS * i;
+    const uint32_t st = (uint32_t)src[1];
+    if (src[0] != 0 && st != 0) {
+      uint64_t k[6], start, tag;
+#pragma unroll
+      for (int w = 0; w < 6; w++) k[w] = src[2 + w];
+      hash_key(t, k, &start, &tag);
+      uint64_t p = start, dist = 0;
+      fail = true;
+      for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
+        u64* slot = t.slots + SLOT_WORDS * p;
+        if (atomicCAS(slot, 0ull, (u64)tag) != 0) continue;
+#pragma unroll
+        for (int w = 0; w < 6; w++) slot[2 + w] = k[w];
+        slot[1] = st;
+        fail = false;
+        break;
+      }
+      probe = (uint32_t)(dist < 0xffffffffull ? dist + 1 : 0xffffffffull);
+    }
+  }
+  wave_max_to(ctl + mvk::IX_CTL_MAXPROBE, probe);
+  wave_count_to(ctl + mvk::IX_CTL_ERR, fail);
+}
+
+// The WANTED entries, listed by count / scan / list over the slots
+__device__ inline bool slot_wanted(const u64* slots, uint64_t i, uint64_t n) {
+  return i < n && slots[SLOT_WORDS * i] != 0 && (uint32_t)slots[SLOT_WORDS * i + 1] == MV_REF_WANTED;
+}
+__global__ void __launch_bounds__(WG) k_ix_wanted_count(const u64* __restrict__ slots, uint64_t n,
+                                                        uint64_t* __restrict__ wgcount) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t tot;
+  (void)wg_excl(slot_wanted(slots, i, n), &tot);
+  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(WG) k_ix_wanted_list(const u64* __restrict__ slots, uint64_t n,
+                                                       const uint64_t* __restrict__ wgbase, uint64_t* __restrict__ out,
+                                                       uint64_t cap) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  const bool w = slot_wanted(slots, i, n);
+  uint64_t tot;
+  const uint64_t r = wgbase[blockIdx.x] + wg_excl(w, &tot);
+  if (!w || r >= cap) return;
+#pragma unroll
+  for (int k = 0; k < 6; k++) out[6 * r + k] = slots[SLOT_WORDS * i + 2 + k];
+}
+
+// ---------------------------------------------------------------- the accept call
+using mvk::AcceptArrays;
+
+__device__ inline bool block_inside(const AcceptArrays& a, uint64_t i) {
+  return a.off[i] <= a.buf_bytes && a.len[i] <= a.buf_bytes - a.off[i];
+}
+
+// KNOWN: the block's own reference is HAVE in the index as it stands (net_sync.rs:325-336);
+// counts the blocks that go on to verify per workgroup
+__global__ void __launch_bounds__(WG) k_acc_probe(IndexTable t, AcceptArrays a, u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint32_t probe = 0;
+  bool fail = false, known = false;
+  if (i < a.n) {
+    const uint64_t len = a.len[i];
+    if (t.slots && block_inside(a, i) && br::own_ref_readable(len)) {
+      const uint8_t* p = a.buf + a.off[i];
+      if (ld64(p + br::LEN_WORD_OFF) == br::DIGEST_LEN) {
+        uint64_t k[6];
+#pragma unroll
+        for (int w = 0; w < 6; w++) k[w] = ld64(p + br::key_word_off(w));
+        known = lookup(t, k, &probe, &fail) == MV_REF_HAVE;
+      }
+    }
+    a.known[i] = known;
+  }
+  uint64_t tot;
+  (void)wg_excl(i < a.n && !known, &tot);
+  if (threadIdx.x == 0) a.wg_a[blockIdx.x] = tot;
+  wave_max_to(ctl + mvk::IX_CTL_MAXPROBE, probe);
+  wave_count_to(ctl + mvk::IX_CTL_ERR, fail);
+}
+
+// the blocks to verify, in order
+__global__ void __launch_bounds__(WG) k_acc_vlist(AcceptArrays a) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  const bool v = i < a.n && !a.known[i];
+  uint64_t tot;
+  const uint64_t r = a.base_a[blockIdx.x] + wg_excl(v, &tot);
+  if (!v) return;
+  a.v_off[r] = a.off[i];
+  a.v_len[r] = a.len[i];
+  a.rank[i] = (uint32_t)r;
+}
+
+__device__ inline bool group_head(const AcceptArrays& a, uint64_t i) {
+  return i < a.n && (i == 0 || a.grp[i] != a.grp[i - 1]);
+}
+__global__ void __launch_bounds__(WG) k_acc_heads(AcceptArrays a) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t tot;
+  (void)wg_excl(group_head(a, i), &tot);
+  if (threadIdx.x == 0) a.wg_a[blockIdx.x] = tot;
+}
+
+// statuses (KNOWN blocks are MV_BLOCK_OK unverified), the group of every block, and a reject flag
+// per group: one rejected block drops its message before add_blocks (net_sync.rs:352-361)
+__global__ void __launch_bounds__(WG) k_acc_groups(AcceptArrays a) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t g = i;
+  if (a.grp) {
+    const bool head = group_head(a, i);
+    uint64_t tot;
+    g = a.base_a[blockIdx.x] + wg_excl(head, &tot) + head - 1;  // heads up to and including i, less one
+  }
+  if (i >= a.n) return;
+  const bool known = a.known[i];
+  const uint8_t st = known ? (uint8_t)MV_BLOCK_OK : a.v_status[a.rank[i]];
+  a.status[i] = st;
+  a.gidx[i] = (uint32_t)g;
+  if (!known && st != MV_BLOCK_OK) atomicMax(a.gflag + g, 1u);
+}
+
+// states before the duplicates are told apart (candidates are MV_ACC_NEW for now), the include
+// count of every candidate, and the per-workgroup counts of both
+__global__ void __launch_bounds__(WG) k_acc_states(AcceptArrays a) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool cand = false;
+  uint64_t k = 0;
+  if (i < a.n) {
+    uint8_t s;
+    if (a.known[i]) s = MV_ACC_KNOWN;
+    else if (a.status[i] != MV_BLOCK_OK) s = MV_ACC_REJECTED;
+    else if (a.gflag[a.gidx[i]]) s = MV_ACC_DROPPED;
+    else s = MV_ACC_NEW, cand = true;
+    // (a block that parsed holds its own reference and its includes; checked again all the same)
+    const uint64_t len = a.len[i];
+    if (cand && !(block_inside(a, i) && br::own_ref_readable(len))) s = MV_ACC_REJECTED, cand = false;
+    if (cand && br::inc_count_readable(len)) {
+      k = ld64(a.buf + a.off[i] + br::INC_COUNT_OFF);
+      if (!br::includes_inside(len, k)) k = 0;
+    }
+    a.state[i] = s;
+    a.kc[i] = (uint32_t)k;
+  }
+  uint64_t tc, tk;
+  (void)wg_excl(cand, &tc);
+  (void)wg_excl(k, &tk);
+  if (threadIdx.x == 0) {
+    a.wg_a[blockIdx.x] = tc;
+    a.wg_b[blockIdx.x] = tk;
+  }
+}
+
+// the candidates in block order: block, where its own reference lies, its first include's number
+__global__ void __launch_bounds__(WG) k_acc_cand_list(AcceptArrays a) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  const bool cand = i < a.n && a.state[i] == MV_ACC_NEW;
+  const uint64_t k = cand ? a.kc[i] : 0;
+  uint64_t tc, tk;
+  const uint64_t r = a.base_a[blockIdx.x] + wg_excl(cand, &tc);
+  const uint64_t ib = a.base_b[blockIdx.x] + wg_excl(k, &tk);
+  if (!cand) return;
+  a.cand_blk[r] = (uint32_t)i;
+  a.cand_src[r] = a.off[i];
+  a.inc_base[r] = ib;
+}
+
+// the lowest block of every reference is NEW, the others DUP (block_manager.rs:68-72)
+__global__ void __launch_bounds__(WG) k_acc_own_states(AcceptArrays a, const u64* __restrict__ item, uint64_t ncand) {
+  const uint64_t r = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (r >= ncand) return;
+  const u64 c = code_of(item[r]);
+  a.state[a.cand_blk[r]] = (c == C_NEW || c == C_RAISED) ? MV_ACC_NEW : MV_ACC_DUP;
+}
+
+// one lane per include of the candidates: where it lies, or IX_NO_SRC when its block is not NEW
+__global__ void __launch_bounds__(WG) k_acc_inc_src(AcceptArrays a, uint64_t ncand, uint64_t ninc,
+                                                    uint64_t* __restrict__ inc_src) {
+  const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (j >= ninc) return;
+  uint64_t lo = 0, hi = ncand;  // the last candidate whose first include is <= j
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (a.inc_base[mid] <= j) lo = mid;
+    else hi = mid;
+  }
+  const uint64_t q = j - a.inc_base[lo];
+  const bool is_new = a.state[a.cand_blk[lo]] == MV_ACC_NEW && q < a.kc[a.cand_blk[lo]];
+  inc_src[j] = is_new ? a.cand_src[lo] + br::include_off(q) : mvk::IX_NO_SRC;
+}
+
+// the includes that created an entry are the missing references, in (block, include) order
+__global__ void __launch_bounds__(WG) k_acc_miss_count(const u64* __restrict__ item, uint64_t n,
+                                                       uint64_t* __restrict__ wgcount) {
+  const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t tot;
+  (void)wg_excl(j < n && code_of(item[j]) == C_NEW, &tot);
+  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(WG) k_acc_miss_list(IndexTable t, const u64* __restrict__ item, uint64_t n,
+                                                      const uint64_t* __restrict__ wgbase, uint64_t* __restrict__ out,
+                                                      uint64_t cap) {
+  const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  const bool m = j < n && code_of(item[j]) == C_NEW;
+  uint64_t tot;
+  const uint64_t r = wgbase[blockIdx.x] + wg_excl(m, &tot);
+  if (!m || r >= cap) return;
+  const u64* slot = t.slots + SLOT_WORDS * (item[j] & SLOT_MASK);
+#pragma unroll
+  for (int k = 0; k < 6; k++) out[6 * r + k] = slot[2 + k];
+}
+
+static inline uint32_t grid_of(uint64_t items) { return (uint32_t)((items + WG - 1) / WG); }
+
+}  // namespace ix
+}  // namespace mv
+
+namespace mvk {
+
+using namespace mv::ix;
+
+uint64_t index_groups(uint64_t n) { return (n + WG - 1) / WG; }
+
+hipError_t launch_index_scan(const uint64_t* wgcount, uint64_t nwg, uint64_t* wgbase, uint64_t* total, hipStream_t s) {
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wgcount, nwg, wgbase, total);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_round(const IndexTable& t, const IndexKeys& ks, uint64_t n, uint64_t* item, uint32_t state,
+                              int round, uint64_t* ctl, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  u64* c = (u64*)ctl;
+  const dim3 g(grid_of(n)), b(WG);
+  hipLaunchKernelGGL(k_ix_claim, g, b, 0, s, t, ks, n, (u64*)item, state, round, c);
+  hipLaunchKernelGGL(k_ix_fill, g, b, 0, s, t, ks, n, (u64*)item, state, c);
+  hipLaunchKernelGGL(k_ix_settle, g, b, 0, s, t, ks, n, (u64*)item, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_giveup(uint64_t* ctl, hipStream_t s) {
+  hipLaunchKernelGGL(k_ix_giveup, dim3(1), dim3(64), 0, s, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_prior(const uint64_t* item, uint64_t n, uint8_t* prior, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ix_prior, dim3(grid_of(n)), dim3(WG), 0, s, (const u64*)item, n, prior);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_lookup(const IndexTable& t, const IndexKeys& ks, uint64_t n, uint8_t* out, uint64_t* ctl,
+                               hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ix_lookup, dim3(grid_of(n)), dim3(WG), 0, s, t, ks, n, out, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_rebuild(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* ctl,
+                                hipStream_t s) {
+  if (n_old == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ix_rebuild, dim3(grid_of(n_old)), dim3(WG), 0, s, (const u64*)old_slots, n_old, t, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_index_wanted(const IndexTable& t, uint64_t* wgcount, uint64_t* wgbase, uint64_t* total, uint64_t* out,
+                               uint64_t cap, hipStream_t s) {
+  const uint64_t n = t.mask + 1;
+  const dim3 g(grid_of(n)), b(WG);
+  hipLaunchKernelGGL(k_ix_wanted_count, g, b, 0, s, (const u64*)t.slots, n, wgcount);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wgcount, index_groups(n), wgbase, total);
+  if (cap) hipLaunchKernelGGL(k_ix_wanted_list, g, b, 0, s, (const u64*)t.slots, n, wgbase, out, cap);
+  return hipGetLastError();
+}
+
+hipError_t launch_accept_probe(const IndexTable& t, const AcceptArrays& a, uint64_t* ctl, hipStream_t s) {
+  const dim3 g(grid_of(a.n)), b(WG);
+  hipLaunchKernelGGL(k_acc_probe, g, b, 0, s, t, a, (u64*)ctl);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, a.wg_a, index_groups(a.n), a.base_a, ctl + IX_CTL_NVER);
+  hipLaunchKernelGGL(k_acc_vlist, g, b, 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_accept_groups(const AcceptArrays& a, uint64_t* ctl, hipStream_t s) {
+  const dim3 g(grid_of(a.n)), b(WG);
+  const uint64_t nwg = index_groups(a.n);
+  if (a.grp) {
+    hipLaunchKernelGGL(k_acc_heads, g, b, 0, s, a);
+    hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, a.wg_a, nwg, a.base_a, ctl + IX_CTL_NHEADS);
+  }
+  hipLaunchKernelGGL(k_acc_groups, g, b, 0, s, a);
+  hipLaunchKernelGGL(k_acc_states, g, b, 0, s, a);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, a.wg_a, nwg, a.base_a, ctl + IX_CTL_NCAND);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, a.wg_b, nwg, a.base_b, ctl + IX_CTL_NINC);
+  hipLaunchKernelGGL(k_acc_cand_list, g, b, 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_accept_own_states(const AcceptArrays& a, const uint64_t* item, uint64_t ncand, hipStream_t s) {
+  if (ncand == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_acc_own_states, dim3(grid_of(ncand)), dim3(WG), 0, s, a, (const u64*)item, ncand);
+  return hipGetLastError();
+}
+
+hipError_t launch_accept_inc_src(const AcceptArrays& a, uint64_t ncand, uint64_t ninc, uint64_t* inc_src, hipStream_t s) {
+  if (ninc == 0 || ncand == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_acc_inc_src, dim3(grid_of(ninc)), dim3(WG), 0, s, a, ncand, ninc, inc_src);
+  return hipGetLastError();
+}
+
+hipError_t launch_accept_missing(const IndexTable& t, const uint64_t* item, uint64_t ninc, uint64_t* wgcount,
+                                 uint64_t* wgbase, uint64_t* ctl, uint64_t* out, uint64_t cap, hipStream_t s) {
+  if (ninc == 0) return hipSuccess;
+  const dim3 g(grid_of(ninc)), b(WG);
+  hipLaunchKernelGGL(k_acc_miss_count, g, b, 0, s, (const u64*)item, ninc, wgcount);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wgcount, index_groups(ninc), wgbase, ctl + IX_CTL_NMISS);
+  if (cap) hipLaunchKernelGGL(k_acc_miss_list, g, b, 0, s, t, (const u64*)item, ninc, wgbase, out, cap);
+  return hipGetLastError();
+}
+
+}  // namespace mvk

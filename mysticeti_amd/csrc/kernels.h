@@ -58,6 +58,8 @@ struct Knobs {
   int64_t prep_chain = 1;                // MV_PREP_CHAIN: a batch's k_bv_prep starts after the previous batch's
                                          // (1: on the engine's streams; 2: on callers' streams too)
   int64_t blk_walk = 1;                  // MV_BLK_WALK: batch-size block calls in one pass over the bincode (k_block_walk); 0: staged pre-image
+  // the index of block references (index.hip)
+  int64_t index_tag_bits = 64;           // MV_INDEX_TAG_BITS: bits kept of a slot's tag (1..64; tests force collisions)
 };
 
 size_t verify_scratch_bytes(uint32_t n);
@@ -427,4 +429,76 @@ hipError_t launch_stream_cut(const uint64_t* soff, uint64_t buf_bytes, uint32_t 
 hipError_t launch_frame_verdicts(uint32_t* rows, uint64_t n_rows, const uint8_t* blk_status, uint64_t n_blk,
                                  uint32_t ns, const uint32_t* kept, const uint32_t* row_base, uint32_t* drop_msg,
                                  hipStream_t s);
+// index.hip: the index of block references and the accept call (rules: block_ref.h; the table, the
+// insert protocol and its memory model are described at the top of index.hip).
+struct IndexTable {
+  unsigned long long* slots;  // mask + 1 slots of 8 words (null: no table yet, every lookup is ABSENT)
+  uint64_t mask;
+  uint64_t k0, k1;    // the context's hash secret
+  uint32_t tag_bits;  // MV_INDEX_TAG_BITS as it stood when the table was made
+};
+// Where the keys of n items lie: item i's six words at base + (off ? off[i] : i * stride) -- an
+// off of IX_NO_SRC skips the item -- consecutive, or (ref) laid out as a bincode BlockReference.
+struct IndexKeys {
+  const uint8_t* base;
+  const uint64_t* off;
+  uint64_t stride;
+  int ref;
+};
+constexpr uint64_t IX_NO_SRC = ~0ull;
+constexpr uint64_t IX_MAX_ITEMS = 0xfffffffeull;  // items of one insert (the owner word holds ~item)
+// control words (device, u64): the HAVE and WANTED entries, the longest probe since the last clear,
+// items left for another round, probes that ran through the table (sticky: MV_E_HIP), then the
+// totals of the accept call's scans and of the WANTED list
+constexpr int IX_CTL_HAVE = 0, IX_CTL_WANTED = 1, IX_CTL_MAXPROBE = 2, IX_CTL_RETRY = 3, IX_CTL_ERR = 4,
+              IX_CTL_NVER = 5, IX_CTL_NHEADS = 6, IX_CTL_NCAND = 7, IX_CTL_NINC = 8, IX_CTL_NMISS = 9,
+              IX_CTL_NWANTED = 10, IX_CTL_WORDS = 16;
+uint64_t index_groups(uint64_t n);  // workgroups of the per-item kernels: wgcount / wgbase hold one word each
+hipError_t launch_index_scan(const uint64_t* wgcount, uint64_t nwg, uint64_t* wgbase, uint64_t* total, hipStream_t s);
+// one insert round (k_ix_claim, k_ix_fill, k_ix_settle) of n items towards `state`; item: n words
+// of per-item records, kept between rounds; round > 0 takes the items the last round left over
+// (ctl[IX_CTL_RETRY], zeroed by the caller before each round)
+hipError_t launch_index_round(const IndexTable& t, const IndexKeys& ks, uint64_t n, uint64_t* item, uint32_t state,
+                              int round, uint64_t* ctl, hipStream_t s);
+// ctl[IX_CTL_ERR] += ctl[IX_CTL_RETRY]: ends the rounds of a call that cannot read the counter back
+hipError_t launch_index_giveup(uint64_t* ctl, hipStream_t s);
+hipError_t launch_index_prior(const uint64_t* item, uint64_t n, uint8_t* prior, hipStream_t s);
+hipError_t launch_index_lookup(const IndexTable& t, const IndexKeys& ks, uint64_t n, uint8_t* out, uint64_t* ctl,
+                               hipStream_t s);
+// every entry of the old table into t (empty, zeroed)
+hipError_t launch_index_rebuild(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* ctl,
+                                hipStream_t s);
+// count / scan / list of the WANTED entries: *total, the first cap into out (cap x 6 words)
+hipError_t launch_index_wanted(const IndexTable& t, uint64_t* wgcount, uint64_t* wgbase, uint64_t* total, uint64_t* out,
+                               uint64_t cap, hipStream_t s);
+struct AcceptArrays {  // one accept call: the caller's blocks and the per-block / per-workgroup scratch
+  const uint8_t* buf;
+  uint64_t buf_bytes;
+  const uint64_t* off;
+  const uint64_t* len;
+  const uint64_t* grp;  // may be null: every block its own group
+  uint64_t n;
+  uint8_t* known;       // per block
+  uint32_t* rank;       // per block that is not KNOWN: its place in the verify list
+  uint64_t* v_off;      // the verify list
+  uint64_t* v_len;
+  uint8_t* v_status;
+  uint8_t* status;      // per block: MV_BLOCK_*
+  uint8_t* state;       // per block: MV_ACC_*
+  uint32_t* gidx;       // per block: its group's number
+  uint32_t* gflag;      // per group: a block of it was rejected (zeroed by the caller)
+  uint32_t* kc;         // per block: includes of a candidate
+  uint64_t *wg_a, *wg_b, *base_a, *base_b;  // per workgroup: two counts and their scans
+  uint32_t* cand_blk;   // per candidate (OK block of an accepted group), in block order: the block,
+  uint64_t* cand_src;   // the offset of its own reference,
+  uint64_t* inc_base;   // the number of its first include among all candidates' includes
+};
+// k_acc_probe, scan, k_acc_vlist: known[], ctl[IX_CTL_NVER] and the verify list
+hipError_t launch_accept_probe(const IndexTable& t, const AcceptArrays& a, uint64_t* ctl, hipStream_t s);
+// after the block pipeline: k_acc_groups, k_acc_states, the candidate list; ctl[IX_CTL_NCAND], ctl[IX_CTL_NINC]
+hipError_t launch_accept_groups(const AcceptArrays& a, uint64_t* ctl, hipStream_t s);
+hipError_t launch_accept_own_states(const AcceptArrays& a, const uint64_t* item, uint64_t ncand, hipStream_t s);
+hipError_t launch_accept_inc_src(const AcceptArrays& a, uint64_t ncand, uint64_t ninc, uint64_t* inc_src, hipStream_t s);
+hipError_t launch_accept_missing(const IndexTable& t, const uint64_t* item, uint64_t ninc, uint64_t* wgcount,
+                                 uint64_t* wgbase, uint64_t* ctl, uint64_t* out, uint64_t cap, hipStream_t s);
 }  // namespace mvk

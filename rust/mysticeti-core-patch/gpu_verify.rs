@@ -161,6 +161,72 @@ impl GpuVerifier {
         out.blk_status.truncate(b);
         Ok(out)
     }
+
+    /// Seeds the index of block references with references the store holds (MV_REF_HAVE): the
+    /// genesis references, and after a replay the rows' words 3..8 (BlockStore::open's
+    /// add_unloaded, block_store.rs:398-404). `refs` holds six words per reference: authority,
+    /// round, the four little-endian digest words.
+    pub fn index_insert_have(&self, refs: &[u64]) -> eyre::Result<()> {
+        ensure!(refs.len() % 6 == 0, "six words per reference");
+        let rc = unsafe {
+            sys::mv_index_insert(self.ctx, refs.as_ptr(), (refs.len() / 6) as u64, sys::MV_REF_HAVE as u32,
+                                 std::ptr::null_mut())
+        };
+        ensure!(rc == sys::MV_OK, "mv_index_insert: {}", self.last_error());
+        Ok(())
+    }
+
+    /// BlockManager::missing_blocks (block_manager.rs:138-140) as the index holds it: the
+    /// MV_REF_WANTED references, six words each, in no particular order.
+    pub fn index_wanted(&self) -> eyre::Result<Vec<u64>> {
+        let mut n = 0u64;
+        let rc = unsafe { sys::mv_index_wanted(self.ctx, std::ptr::null_mut(), 0, &mut n) };
+        ensure!(rc == sys::MV_OK, "mv_index_wanted: {}", self.last_error());
+        let mut out = vec![0u64; 6 * n as usize];
+        let rc = unsafe { sys::mv_index_wanted(self.ctx, out.as_mut_ptr(), n, &mut n) };
+        ensure!(rc == sys::MV_OK, "mv_index_wanted: {}", self.last_error());
+        out.truncate(6 * n as usize);
+        Ok(out)
+    }
+
+    /// process_blocks (net_sync.rs:314-386) for the blocks of several received messages in one
+    /// call: the `processed` query and skip (:325-336), StatementBlock::verify of the others, the
+    /// early return of a message with a rejected block (:352-361), and the include lookups of
+    /// BlockManager::add_blocks (block_manager.rs:62-98) whose result the syncer requests from
+    /// peers (net_sync.rs:388-398). `groups[i]` names the message of block i (non-decreasing).
+    /// The caller hands the MV_ACC_NEW blocks to the core, which keeps the suspend / unlock
+    /// cascade (blocks_pending) and the WAL write.
+    pub fn accept_blocks(&self, buf: &[u8], blocks: &[(u64, u64)], groups: &[u64]) -> eyre::Result<Accepted> {
+        ensure!(groups.len() == blocks.len(), "one group word per block");
+        let n = blocks.len();
+        let off: Vec<u64> = blocks.iter().map(|b| b.0).collect();
+        let len: Vec<u64> = blocks.iter().map(|b| b.1).collect();
+        let mut out = Accepted { blk_status: vec![0; n], blk_state: vec![0; n], missing: Vec::new() };
+        let cap = 64 * n.max(1);
+        out.missing.resize(6 * cap, 0);
+        let mut n_missing = 0u64;
+        let rc = unsafe {
+            sys::mv_accept_blocks(self.ctx, buf.as_ptr(), off.as_ptr(), len.as_ptr(), groups.as_ptr(), n as u32,
+                                  out.blk_status.as_mut_ptr(), out.blk_state.as_mut_ptr(), out.missing.as_mut_ptr(),
+                                  cap as u64, &mut n_missing)
+        };
+        ensure!(rc == sys::MV_OK, "mv_accept_blocks: {}", self.last_error());
+        if n_missing as usize <= cap {
+            out.missing.truncate(6 * n_missing as usize);
+        } else {
+            // the list was cut: the index holds these references as WANTED already (a second accept
+            // call would find every block KNOWN), so the whole set comes from there
+            out.missing = self.index_wanted()?;
+        }
+        Ok(out)
+    }
+}
+
+/// Result of `GpuVerifier::accept_blocks` (layout: include/mysti_verify.h, mv_accept_blocks).
+pub struct Accepted {
+    pub blk_status: Vec<u8>, // MV_BLOCK_*, MV_BLOCK_OK for blocks skipped as known
+    pub blk_state: Vec<u8>,  // MV_ACC_*
+    pub missing: Vec<u64>,   // six words per reference to request from peers
 }
 
 /// Result of `GpuVerifier::wal_replay` (layout: include/mysti_verify.h, mv_wal_replay).
