@@ -19,11 +19,10 @@
 //   k_bv_prep     lane per signature: SHA-512 challenge, ZIP-215 decode of A and R,
 //                 z_i = BLAKE2b(secret || call || i), scalars z_i and z_i k_i mod l,
 //                 affine points (y+x, y-x, 2dxy) to HBM, sum z_i s_i
-//   k_part_*, k_fine_sort   two-pass counting sort of the (bucket, point) entries
-//                 (LDS histograms and ranks; no global atomics; the _lds forms stage
-//                 their output in LDS and store it coalesced)
-//   k_bv_bucket   lane per bucket: the bucket's sum T (k_bv_bucket_bal + _fix: the
-//                 same sums with an equal number of entries per lane)
+//   k_part_*, k_fine_sort_lds   two-pass counting sort of the (bucket, point) entries
+//                 (LDS histograms and ranks; no global atomics; output staged in LDS
+//                 and stored coalesced)
+//   k_bv_bucket_bal + _fix   every bucket's sum T, an equal number of entries per lane
 //   k_bv_reduce   tree over the buckets (fan-in 8) of the pairs (V, T) per window
 //                 (_q: four lanes per element, _r: a wave per element on small levels)
 //   k_bv_final    Horner over the 16 window sums (one DPP row per coordinate with one
@@ -349,9 +348,9 @@ __global__ void __launch_bounds__(256, MV_PREP_OCC)
 // Two-pass counting sort of the (bucket key, point) entries without global atomics:
 //   k_part_count               chunk = 1024 signatures: entries per partition (LDS)
 //   k_part_scan / k_part_top   exclusive offsets of every (chunk, partition) run
-//   k_part_scatter             per chunk: entries (key, point) into their
+//   k_part_scatter_lds         per chunk: entries (key, point) into their
 //                              partition, runs ordered by chunk, ranks from LDS atomics
-//   k_fine_sort                workgroup per partition: counting sort by the low 8 key
+//   k_fine_sort_lds            workgroup per partition: counting sort by the low 8 key
 //                              bits in LDS -> final bucket lists and bucket offsets
 // Sub-batches (groups): the batch's chunks are cut into `count` contiguous groups of `cpg`
 // chunks, and every group has its own buckets (key = g * BV_NKG + local key), so the
@@ -454,43 +453,15 @@ __global__ void __launch_bounds__(256) k_part_top(const uint32_t* __restrict__ p
   }
   if (threadIdx.x == 0) pstart[total] = all;
 }
+// The scatter, with coalesced stores: window by window, the block's entries are first placed in
+// LDS in partition order (the chunk's per-partition counts from k_part_count, scanned), then
+// thread i stores LDS entry i, so consecutive threads write consecutive words of a partition's
+// run instead of one scattered 8-byte word per entry (the direct form, removed, wrote 2.7x the
+// entry bytes, profiles/r05/pmc/pmc_c2_k_part_scatter.txt). Entry order inside a run is
+// arbitrary, which no later stage depends on (the fine sort orders by key, and a bucket's sum
+// does not depend on the order of its points).
 // (scal, n: the signatures [base, base + n) of a batch of nall; point refs are batch-wide)
-__global__ void __launch_bounds__(PART_CHUNK) k_part_scatter(const uint4* __restrict__ scal, uint32_t n,
-                                                             const uint32_t* __restrict__ poff,
-                                                             const uint32_t* __restrict__ pstart, BvGroups G,
-                                                             uint32_t skipA, uint32_t nall, uint32_t base,
-                                                             unsigned long long* __restrict__ tmp) {
-  __shared__ uint32_t rank[BV_NPG];
-  for (int i = threadIdx.x; i < BV_NPG; i += PART_CHUNK) rank[i] = 0;
-  __syncthreads();
-  const uint32_t gid = blockIdx.x * PART_CHUNK + threadIdx.x;
-  if (gid < n) {
-    const uint32_t g = blockIdx.x / G.cpg;
-    uint32_t z[4], zk[8];
-    load_scalars(z, zk, scal, gid);
-    if (skipA) {
-#pragma unroll
-      for (int i = 0; i < 8; i++) zk[i] = 0;
-    }
-    const uint32_t* po = poff + (size_t)blockIdx.x * BV_NPG;
-    const uint32_t* ps = pstart + (size_t)g * BV_NPG;
-    bv_for_digits(z, zk, [&](int w, int d, int isA) {
-      const uint32_t key = bv_key(w, d);
-      const uint32_t p = key >> BV_FINE_BITS;
-      const uint32_t r = atomicAdd(&rank[p], 1u);
-      const uint32_t pt = isA ? nall + base + gid : base + gid;
-      tmp[ps[p] + po[p] + r] = ((unsigned long long)(g * BV_NKG + key) << 32) | (pt << 1) | (d < 0 ? 1u : 0u);
-    });
-  }
-}
-// The same scatter with coalesced stores (MV_SCATTER_LDS): window by window, the block's entries
-// are first placed in LDS in partition order (the chunk's per-partition counts from
-// k_part_count, scanned), then thread i stores LDS entry i, so consecutive threads write
-// consecutive words of a partition's run instead of one scattered 8-byte word per entry (the
-// direct form wrote 2.7x the entry bytes, profiles/r05/pmc/pmc_c2_k_part_scatter.txt). Entry
-// order inside a run changes, which no later stage depends on (the fine sort orders by key,
-// and a bucket's sum does not depend on the order of its points).
-constexpr uint32_t BV_PPW_ = BV_NB >> BV_FINE_BITS;  // partitions per window (128)
+constexpr uint32_t BV_PPW = BV_NB >> BV_FINE_BITS;  // partitions per window (128)
 __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __restrict__ scal, uint32_t n,
                                                                  const uint32_t* __restrict__ pcount,
                                                                  const uint32_t* __restrict__ poff,
@@ -498,7 +469,7 @@ __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __
                                                                  uint32_t skipA, uint32_t nall, uint32_t base,
                                                                  unsigned long long* __restrict__ tmp) {
   __shared__ unsigned long long buf[2 * PART_CHUNK];  // one window's entries (<= 2 per signature)
-  __shared__ uint32_t lofs[BV_PPW_ + 1], gpos[BV_PPW_], rank[BV_PPW_];
+  __shared__ uint32_t lofs[BV_PPW + 1], gpos[BV_PPW], rank[BV_PPW];
   const uint32_t gid = blockIdx.x * PART_CHUNK + threadIdx.x;
   const bool live = gid < n;
   const uint32_t g = blockIdx.x / G.cpg;
@@ -527,7 +498,7 @@ __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __
   for (int w = 0; w < BV_NW; w++) {
     // this window's partitions: chunk-local offsets (wave 0 scans 128 counts), global run starts
     if (threadIdx.x < 64) {
-      const uint32_t l = threadIdx.x, p0 = (uint32_t)w * BV_PPW_ + 2 * l;
+      const uint32_t l = threadIdx.x, p0 = (uint32_t)w * BV_PPW + 2 * l;
       const uint32_t c0 = pc[p0], c1 = pc[p0 + 1];
       uint32_t incl = c0 + c1;
 #pragma unroll
@@ -538,7 +509,7 @@ __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __
       const uint32_t ex = incl - c0 - c1;
       lofs[2 * l] = ex;
       lofs[2 * l + 1] = ex + c0;
-      if (l == 63) lofs[BV_PPW_] = incl;
+      if (l == 63) lofs[BV_PPW] = incl;
       gpos[2 * l] = ps[p0] + po[p0];
       gpos[2 * l + 1] = ps[p0 + 1] + po[p0 + 1];
       rank[2 * l] = 0;
@@ -546,17 +517,17 @@ __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __
     }
     __syncthreads();
     auto place = [&](int d, uint32_t pt) {
-      const uint32_t key = bv_key(w, d), pl = (key >> BV_FINE_BITS) & (BV_PPW_ - 1);
+      const uint32_t key = bv_key(w, d), pl = (key >> BV_FINE_BITS) & (BV_PPW - 1);
       const uint32_t r = atomicAdd(&rank[pl], 1u);
       buf[lofs[pl] + r] = ((unsigned long long)(g * BV_NKG + key) << 32) | (pt << 1) | (d < 0 ? 1u : 0u);
     };
     if (w < 8 && dR[w]) place(dR[w], ptR);
     if (dA[w]) place(dA[w], ptA);
     __syncthreads();
-    const uint32_t tot = lofs[BV_PPW_];
+    const uint32_t tot = lofs[BV_PPW];
     for (uint32_t i = threadIdx.x; i < tot; i += PART_CHUNK) {
       const unsigned long long e = buf[i];
-      const uint32_t pl = ((uint32_t)(e >> 32) >> BV_FINE_BITS) & (BV_PPW_ - 1);
+      const uint32_t pl = ((uint32_t)(e >> 32) >> BV_FINE_BITS) & (BV_PPW - 1);
       tmp[gpos[pl] + (i - lofs[pl])] = e;
     }
     __syncthreads();
@@ -565,65 +536,19 @@ __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __
 
 // block -> partition P: the partition's entries sorted by bucket into ents; offs[key] for
 // its 256 keys. FINE_NT threads over 256 bins (a partition holds ~8K entries, window 15's
-// ~32K: digits stop at 2^13), so the ranked stores of the blocks in flight merge in L2. The
-// biggest partitions (window 15's) of every group are scheduled first.
-constexpr uint32_t BV_PPW = BV_NB >> BV_FINE_BITS;  // partitions per window (128)
-constexpr int FINE_NT = 1024;
-__global__ void __launch_bounds__(FINE_NT) k_fine_sort(const unsigned long long* __restrict__ tmp,
-                                                       const uint32_t* __restrict__ pstart, uint32_t ngroups,
-                                                       uint32_t* __restrict__ ents, uint32_t* __restrict__ offs) {
-  constexpr int NF = 1 << BV_FINE_BITS;
-  __shared__ uint32_t cnt[NF];
-  const uint32_t span = ngroups * BV_PPW;
-  const uint32_t w = BV_NW - 1 - blockIdx.x / span;
-  const uint32_t g = (blockIdx.x % span) / BV_PPW;
-  const uint32_t p = g * BV_NPG + w * BV_PPW + blockIdx.x % BV_PPW;
-  const uint32_t s = pstart[p], e = pstart[p + 1];
-  if (threadIdx.x < NF) cnt[threadIdx.x] = 0;
-  __syncthreads();
-  for (uint32_t i = s + threadIdx.x; i < e; i += FINE_NT) atomicAdd(&cnt[(uint32_t)(tmp[i] >> 32) & (NF - 1)], 1u);
-  __syncthreads();
-  static_assert(NF == 256, "wave 0 scans four bins per lane");
-  if (threadIdx.x < 64) {  // wave 0 alone (no barrier inside): exclusive scan of the bins
-    const uint32_t l = threadIdx.x;
-    uint32_t c[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      c[k] = cnt[4 * l + k];
-      sum += c[k];
-    }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t x = (uint32_t)__shfl_up((int)incl, o);
-      if (l >= (uint32_t)o) incl += x;
-    }
-    uint32_t ex = incl - sum;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      offs[(size_t)p * NF + 4 * l + k] = s + ex;
-      cnt[4 * l + k] = ex;
-      ex += c[k];
-    }
-    if (p == ngroups * BV_NPG - 1 && l == 0) offs[(size_t)ngroups * BV_NKG] = e;
-  }
-  __syncthreads();
-  for (uint32_t i = s + threadIdx.x; i < e; i += FINE_NT) {
-    const unsigned long long v = tmp[i];
-    const uint32_t r = atomicAdd(&cnt[(uint32_t)(v >> 32) & (NF - 1)], 1u);
-    ents[s + r] = (uint32_t)v;
-  }
-}
-
-// The same sort with its output staged in LDS (MV_FINE_LDS): a partition of <= FINE_LDS entries
-// is read once into registers (16 per thread) and counted; the count's atomic returns each
-// entry's rank in its bin, so after the scan an entry's place is its bin's start + its rank (one
-// LDS atomic per entry instead of round 5's two); the entries are placed in LDS in bucket order
-// and stored coalesced; the direct form read each entry twice and stored one scattered word per
-// entry. Larger partitions (window 15's at 2^20 signatures: ~32K) take the direct form.
+// ~32K: digits stop at 2^13). The biggest partitions (window 15's) of every group are
+// scheduled first.
+// The output is staged in LDS: a partition of <= FINE_LDS entries is read once into registers
+// (16 per thread) and counted; the count's atomic returns each entry's rank in its bin, so after
+// the scan an entry's place is its bin's start + its rank (one LDS atomic per entry instead of
+// round 5's two); the entries are placed in LDS in bucket order and stored coalesced (sort stage
+// 0.32 -> 0.29 ms, profiles/r05/c2_fine_lds_ab.txt). Larger partitions (window 15's at 2^20
+// signatures: ~32K) take the direct path in the same kernel: each entry is read twice and
+// stored as one scattered word, and the ranked stores of the blocks in flight merge in L2.
 // Bank conflicts stay ~65% of the LDS cycles either way (profiles/r06/pmc_c2s1_k_fine_sort_lds_*):
 // 64 lanes' random bins (and random ranks for the placement) land on 64 banks at random, about
 // four to a bank; the kernel is 0.16 ms of the 3.2-ms step.
+constexpr int FINE_NT = 1024;
 constexpr uint32_t FINE_LDS = 16384;
 constexpr int FINE_FPT = FINE_LDS / FINE_NT;
 __global__ void __launch_bounds__(FINE_NT) k_fine_sort_lds(const unsigned long long* __restrict__ tmp,
@@ -698,111 +623,22 @@ __global__ void __launch_bounds__(FINE_NT) k_fine_sort_lds(const unsigned long l
 }
 
 // ---------------------------------------------------------------- buckets
-// Lane = segment of `seg` consecutive buckets (g, w, j*seg .. j*seg + seg - 1), consumed from
-// the top bucket down: T = running sum of the segment's buckets, V = sum of T after every
-// bucket = sum_b (b + 1) B_{j*seg + b}. The segment then stands for V + (j * seg) T in the
-// window's sum (k_bv_reduce). seg = 1: T only (V = T). Windows are laid out high-first in the
-// grid (window 15's buckets hold four times the entries), every group's windows side by side,
-// and each point is loaded one add ahead.
+// Every lane adds the same number L of entries: one lane per bucket left a wave as slow as its
+// fullest bucket -- bucket sizes are Poisson (mean 32-128 by window), and the wave's max of 64
+// kept lanes busy ~75% of the time (SQ_THREAD_CYCLES_VALU / (64 x SQ_INSTS_VALU),
+// profiles/r05/pmc/pmc_c2_k_bv_bucket.txt; the A/B against that form, removed since:
+// profiles/r05/c2_bucket_bal_ab.txt). Lane j takes entries [j L, (j + 1) L) of the whole
+// key-sorted list (all groups and windows: ents is sorted by key = g * BV_NKG + w * BV_NB +
+// |d| - 1), each point loaded one add ahead. A bucket that starts in the lane's range is
+// written to bktT[key] by it (complete, or its first piece); the piece of a bucket that began
+// before the range goes to carry[j], which k_bv_bucket_fix adds to bktT. Empty buckets are
+// written (identity) by k_bv_bucket_fix too. bktT is the reduction's first-level input: one sum
+// T per bucket key, row (g, w) at (g * BV_NW + w) * BV_NB.
 // 3 workgroups per CU (168 VGPRs, 16 spilled) beat 2 (175 VGPRs, no spill): the gathers
 // need the third wave per SIMD (config 2: bucket 1.71 -> 1.44-1.50 ms as run, +0.8% step rate)
 #ifndef MV_BUCKET_OCC
 #define MV_BUCKET_OCC 3
 #endif
-#ifndef MV_BUCKET_PF2
-#define MV_BUCKET_PF2 1  // k_bv_bucket_bal: unconditional point prefetch (0: the old branch, A/B)
-#endif
-__global__ void __launch_bounds__(256, MV_BUCKET_OCC) k_bv_bucket(const uint4* __restrict__ pts, const uint32_t* __restrict__ offs,
-                                                   const uint32_t* __restrict__ ents, uint32_t ngroups, uint32_t seg,
-                                                   uint32_t nw, uint4* __restrict__ segV, uint4* __restrict__ segT) {
-  const uint32_t nsw = BV_NB / seg;  // segments per (group, window) row
-  const uint32_t lin = blockIdx.x * blockDim.x + threadIdx.x;
-  if (lin >= ngroups * nw * nsw) return;  // windows nw.. carry no entries (per-key A term)
-  const uint32_t span = ngroups * nsw;
-  const uint32_t w = nw - 1 - lin / span;
-  const uint32_t g = (lin % span) / nsw, j = lin % nsw;
-  const uint32_t sidx = (g * BV_NW + w) * nsw + j;  // segment index, row-major
-  const uint32_t key0 = g * BV_NKG + w * BV_NB + j * seg;
-  // the running sum V waits in LDS ([word][thread]: conflict-free) while the bucket's points
-  // are added into T, so it holds no registers across the inner loop (no spill at 3 WG/CU)
-  __shared__ uint32_t sV[36][256];
-  const uint32_t tid = threadIdx.x;
-  auto v_load = [&](p3& V) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      V.X.v[i] = sV[i][tid];
-      V.Y.v[i] = sV[9 + i][tid];
-      V.Z.v[i] = sV[18 + i][tid];
-      V.T.v[i] = sV[27 + i][tid];
-    }
-  };
-  auto v_store = [&](const p3& V) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      sV[i][tid] = V.X.v[i];
-      sV[9 + i][tid] = V.Y.v[i];
-      sV[18 + i][tid] = V.Z.v[i];
-      sV[27 + i][tid] = V.T.v[i];
-    }
-  };
-  p3 T;
-  p3_identity(T);
-  if (seg > 1) v_store(T);  // V = identity
-  const uint32_t e_lo = offs[key0];
-  uint32_t e = offs[key0 + seg];
-  uint4 q[7];
-  uint32_t ent = 0;
-  if (e > e_lo) {
-    e--;
-    ent = ents[e];
-    const uint4* p = pts + (size_t)(ent >> 1) * PT_QUADS;
-#pragma unroll
-    for (int i = 0; i < 7; i++) q[i] = p[i];
-  }
-  uint32_t b1 = offs[key0 + seg];
-  for (int b = (int)seg - 1; b >= 0; b--) {
-    const uint32_t b0 = offs[key0 + b];
-    for (uint32_t k = b1; k > b0; k--) {
-      precomp pc;
-      quads_to_precomp(pc, q);
-      const bool neg = ent & 1u;
-      if (e > e_lo) {  // next point in flight during this add
-        e--;
-        ent = ents[e];
-        const uint4* p = pts + (size_t)(ent >> 1) * PT_QUADS;
-#pragma unroll
-        for (int i = 0; i < 7; i++) q[i] = p[i];
-      }
-      precomp_cneg(pc, neg);
-      p1p1 t;
-      p3_add_precomp(t, T, pc);
-      p1p1_to_p3(T, t);
-    }
-    b1 = b0;
-    if (seg > 1) {
-      p3 V;
-      v_load(V);
-      p3_acc(V, T);
-      v_store(V);
-    }
-  }
-  if (seg > 1) {
-    p3 V;
-    v_load(V);
-    p3_store(segV, sidx, V);
-  }
-  p3_store(segT, sidx, T);
-}
-
-// Balanced buckets (seg = 1, MV_BUCKET_BAL): one lane per bucket leaves a wave as slow as its
-// fullest bucket — bucket sizes are Poisson (mean 32-128 by window), and the wave's max of 64
-// kept lanes busy ~75% of the time (SQ_THREAD_CYCLES_VALU / (64 x SQ_INSTS_VALU),
-// profiles/r05/pmc/pmc_c2_k_bv_bucket.txt). Here every lane adds the same number L of entries:
-// lane j takes entries [j L, (j + 1) L) of the whole key-sorted list (all groups and windows:
-// ents is sorted by key = g * BV_NKG + w * BV_NB + |d| - 1). A bucket that starts in the lane's
-// range is written to segT by it (complete, or its first piece); the piece of a bucket that
-// began before the range goes to carry[j], which k_bv_bucket_fix adds to segT. Empty buckets
-// are written (identity) by k_bv_bucket_fix too.
 // offs_key(x): the largest key k in [k0, nk) with offs[k] <= x (offs nondecreasing, offs[k0] <= x)
 MV_DEV uint32_t bv_key_of(const uint32_t* __restrict__ offs, uint32_t k0, uint32_t nk, uint32_t x) {
   uint32_t lo = k0, hi = nk;  // offs[lo] <= x, answer in [lo, hi)
@@ -817,7 +653,7 @@ __global__ void __launch_bounds__(256, MV_BUCKET_OCC) k_bv_bucket_bal(const uint
                                                                      const uint32_t* __restrict__ offs,
                                                                      const uint32_t* __restrict__ ents, uint32_t nk,
                                                                      uint32_t nlanes, uint4* __restrict__ carry,
-                                                                     uint4* __restrict__ segT) {
+                                                                     uint4* __restrict__ bktT) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= nlanes) return;
   const uint32_t e0 = offs[0], e1 = offs[nk];
@@ -832,15 +668,13 @@ __global__ void __launch_bounds__(256, MV_BUCKET_OCC) k_bv_bucket_bal(const uint
     if (head)
       p3_store(carry, j, P);
     else
-      p3_store(segT, key, P);
+      p3_store(bktT, key, P);
   };
   p3 T;
   p3_identity(T);
   uint4 q[7];
   uint32_t ent = ents[lo];
-#if MV_BUCKET_PF2
   uint32_t ent_n = ents[min(lo + 1, hi - 1)];  // the entry after the one in flight
-#endif
   {
     const uint4* p = pts + (size_t)(ent >> 1) * PT_QUADS;
 #pragma unroll
@@ -850,7 +684,6 @@ __global__ void __launch_bounds__(256, MV_BUCKET_OCC) k_bv_bucket_bal(const uint
     precomp pc;
     quads_to_precomp(pc, q);
     const bool neg = ent & 1u;
-#if MV_BUCKET_PF2
     // next point in flight during this add, loaded unconditionally (the last lap reloads entry
     // hi - 1): a load under a branch made the compiler copy the quads into the loop's registers
     // inside the branch, waiting on the loads at once; and the entry index one lap further ahead
@@ -861,14 +694,6 @@ __global__ void __launch_bounds__(256, MV_BUCKET_OCC) k_bv_bucket_bal(const uint
 #pragma unroll
       for (int i = 0; i < 7; i++) q[i] = p[i];
     }
-#else
-    if (x + 1 < hi) {  // next point in flight during this add
-      ent = ents[x + 1];
-      const uint4* p = pts + (size_t)(ent >> 1) * PT_QUADS;
-#pragma unroll
-      for (int i = 0; i < 7; i++) q[i] = p[i];
-    }
-#endif
     precomp_cneg(pc, neg);
     p1p1 t;
     p3_add_precomp(t, T, pc);
@@ -891,7 +716,7 @@ __global__ void __launch_bounds__(256, MV_BUCKET_OCC) k_bv_bucket_bal(const uint
 // past the lane that began it gets the carries of the lanes it continues into.
 __global__ void __launch_bounds__(256) k_bv_bucket_fix(const uint32_t* __restrict__ offs, uint32_t nk,
                                                        uint32_t ngroups, uint32_t nw, uint32_t nlanes,
-                                                       const uint4* __restrict__ carry, uint4* __restrict__ segT) {
+                                                       const uint4* __restrict__ carry, uint4* __restrict__ bktT) {
   const uint32_t lin = blockIdx.x * blockDim.x + threadIdx.x;
   if (lin >= ngroups * nw * BV_NB) return;
   const uint32_t g = lin / (nw * BV_NB), r = lin % (nw * BV_NB);
@@ -902,31 +727,28 @@ __global__ void __launch_bounds__(256) k_bv_bucket_fix(const uint32_t* __restric
   if (lo == hi) {
     p3 I;
     p3_identity(I);
-    p3_store(segT, key, I);
+    p3_store(bktT, key, I);
     return;
   }
   const uint32_t j0 = (lo - e0) / L, j1 = (hi - 1 - e0) / L;
   if (j1 == j0) return;
   p3 T;
-  p3_load(T, segT, key);
+  p3_load(T, bktT, key);
   for (uint32_t j = j0 + 1; j <= j1; j++) {
     p3 C;
     p3_load(C, carry, j);
     p3_acc(T, C);
   }
-  p3_store(segT, key, T);
+  p3_store(bktT, key, T);
 }
 
 // ---------------------------------------------------------------- reduction
-#ifndef MV_REDUCE_PF
-#define MV_REDUCE_PF 1  // inputs loaded one step ahead (0: the old load-then-use order, A/B)
-#endif
 // Rows = (group, window); row r holds cnt_in elements. Elements (V, T) with indices
 // m = 0..cnt-1 stand for V + (m * scale) T. Groups of FAN consecutive elements m = FAN*q + t
 // become one element with index q:
 //   V' = sum V_t + scale * sum_t t T_t,   T' = sum T_t,   scale' = FAN * scale.
 // scale is a power of two (log2 = shift): the multiplication is `shift` doublings.
-// First level with one bucket per segment (inV == nullptr): the elements are the buckets,
+// First level (inV == nullptr): the elements are the buckets,
 // m = |d| - 1, so V_m = T_m and scale = 1: V' = sum_t (t + 1) T_t, the sum of the running sums.
 // Output rows are compact, r = g * nw + w; the first level (from_keys) reads the bucket
 // kernel's key-space layout, row (g, w) at (g * BV_NW + w) * cnt_in.
@@ -946,16 +768,6 @@ __global__ void __launch_bounds__(64) k_bv_reduce(const uint4* __restrict__ inV,
   p3_identity(Sx);
   // each step's point(s) loaded one step ahead (the lane is a lone latency chain)
   if (!inV) {
-#if MV_REDUCE_PF == 0
-    for (int t = m - 1; t >= 0; t--) {
-      p3_load(X, inT, base + t);
-      p3_acc(U, X);
-      p3_acc(Sx, U);
-    }
-    p3_store(outV, gid, Sx);
-    p3_store(outT, gid, U);
-    return;
-#endif
     p3_load(X, inT, base + m - 1);
     for (int t = m - 1; t >= 0; t--) {
       const p3 Xc = X;
@@ -969,20 +781,6 @@ __global__ void __launch_bounds__(64) k_bv_reduce(const uint4* __restrict__ inV,
   }
   p3 Vs, Y;
   p3_identity(Vs);
-#if MV_REDUCE_PF == 0
-  for (int t = m - 1; t >= 0; t--) {
-    p3_load(X, inT, base + t);
-    p3_acc(U, X);
-    if (t > 0) p3_acc(Sx, U);
-    p3_load(Y, inV, base + t);
-    p3_acc(Vs, Y);
-  }
-  p3_dbl_n(Sx, shift);
-  p3_acc(Vs, Sx);
-  p3_store(outV, gid, Vs);
-  p3_store(outT, gid, U);
-  return;
-#endif
   p3_load(X, inT, base + m - 1);
   p3_load(Y, inV, base + m - 1);
   for (int t = m - 1; t >= 0; t--) {
@@ -1174,16 +972,6 @@ __global__ void __launch_bounds__(256) k_bv_reduce_q(const uint4* __restrict__ i
   qp_identity(Sx);
   // each step's point(s) loaded one step ahead (a quad is a lone latency chain)
   if (!inV) {
-#if MV_REDUCE_PF == 0
-    for (int t = m - 1; t >= 0; t--) {
-      qp_load(X, inT, base + t);
-      qp_add(U, X);
-      qp_add(Sx, U);
-    }
-    qp_store(outV, gid, Sx);
-    qp_store(outT, gid, U);
-    return;
-#endif
     qp_load(X, inT, base + m - 1);
     for (int t = m - 1; t >= 0; t--) {
       const fe Xc = X;
@@ -1197,20 +985,6 @@ __global__ void __launch_bounds__(256) k_bv_reduce_q(const uint4* __restrict__ i
   }
   fe Vs, Y;
   qp_identity(Vs);
-#if MV_REDUCE_PF == 0
-  for (int t = m - 1; t >= 0; t--) {
-    qp_load(X, inT, base + t);
-    qp_add(U, X);
-    if (t > 0) qp_add(Sx, U);
-    qp_load(Y, inV, base + t);
-    qp_add(Vs, Y);
-  }
-  qp_dbl_n(Sx, shift);
-  qp_add(Vs, Sx);
-  qp_store(outV, gid, Vs);
-  qp_store(outT, gid, U);
-  return;
-#endif
   qp_load(X, inT, base + m - 1);
   qp_load(Y, inV, base + m - 1);
   for (int t = m - 1; t >= 0; t--) {
@@ -1402,7 +1176,7 @@ namespace mvk {
 namespace {
 constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct BatchLayout {
-  size_t pts, scal, pcount, poff, ptot, pstart, tmp, offs, ents, segV, segT, rV0, rT0, rV1, rT1, bsum, kpart, keyp,
+  size_t pts, scal, pcount, poff, ptot, pstart, tmp, offs, ents, carry, bktT, rV0, rT0, rV1, rT1, bsum, kpart, keyp,
       asum, flag, total;
   BatchLayout(uint32_t n, uint32_t groups) {
     using namespace mv;
@@ -1418,9 +1192,9 @@ struct BatchLayout {
     tmp = take((size_t)(BV_NWR + BV_NW) * n * 8);
     offs = take(((size_t)groups * BV_NKG + 1) * 4);
     ents = take((size_t)(BV_NWR + BV_NW) * n * 4);
-    // segments of >= 2 buckets, or the balanced bucket kernel's carries (one per lane)
-    segV = take((size_t)groups * BV_NKG / 2 * P3_QUADS * 16);
-    segT = take((size_t)groups * BV_NKG * P3_QUADS * 16);
+    // k_bv_bucket_bal's carries (one per lane, at most BV_NKG / 2 lanes per group)
+    carry = take((size_t)groups * BV_NKG / 2 * P3_QUADS * 16);
+    bktT = take((size_t)groups * BV_NKG * P3_QUADS * 16);
     const size_t lv = (size_t)groups * (BV_NKG / BV_FAN) * P3_QUADS * 16;
     rV0 = take(lv); rT0 = take(lv); rV1 = take(lv); rT1 = take(lv);
     bsum = take((size_t)BV_MAXG * BSUM_WORDS * 8);  // per group
@@ -1445,13 +1219,6 @@ bool agg_disabled(const Knobs& kn) { return kn.no_key_agg != 0; }
 // reduction levels with at most this many elements run four lanes per element
 // (MV_REDUCE_QUAD=<n> for experiments; 0 = never)
 uint32_t reduce_quad_max(const Knobs& kn) { return (uint32_t)kn.reduce_quad; }
-
-// buckets per bucket-kernel lane (a power of two): MV_BV_SEG=<k> for experiments
-uint32_t bucket_segment(const Knobs& kn) {
-  uint32_t seg = kn.bv_seg > 0 ? (uint32_t)kn.bv_seg : 1u;  // 1: measured best for 1..16 groups with the quad reduce
-  if (seg > 64) seg = 64;
-  return 1u << (31 - __builtin_clz(seg));
-}
 }  // namespace
 
 size_t batch_scratch_bytes(uint32_t n, uint32_t groups) { return BatchLayout(n, groups).total; }
@@ -1554,8 +1321,8 @@ hipError_t launch_msm_stage(const Knobs& kn, const uint32_t* key_idx, uint32_t n
   unsigned long long* tmp = (unsigned long long*)(base + L.tmp);
   uint32_t* offs = (uint32_t*)(base + L.offs);
   uint32_t* ents = (uint32_t*)(base + L.ents);
-  uint4* segV = (uint4*)(base + L.segV);
-  uint4* segT = (uint4*)(base + L.segT);
+  uint4* carry = (uint4*)(base + L.carry);
+  uint4* bktT = (uint4*)(base + L.bktT);
   uint4* rv[2] = {(uint4*)(base + L.rV0), (uint4*)(base + L.rV1)};
   uint4* rt[2] = {(uint4*)(base + L.rT0), (uint4*)(base + L.rT1)};
   unsigned long long* bsum = (unsigned long long*)(base + L.bsum);
@@ -1566,48 +1333,29 @@ hipError_t launch_msm_stage(const Knobs& kn, const uint32_t* key_idx, uint32_t n
   const uint32_t nchunk = (n + PART_CHUNK - 1) / PART_CHUNK;
   const uint32_t nparts = G.count * BV_NPG;
   const uint32_t nw = agg ? BV_NWR : BV_NW;  // windows with bucket entries
-  const uint32_t seg = bucket_segment(kn);
   const uint32_t nk = G.count * BV_NKG;
-  // bucket sums of the sorted entries of m signatures
-  auto buckets = [&](uint64_t m) {
-    if (seg == 1 && kn.bucket_bal > 0) {
-      // equal entries per lane (the carries in segV: at most one per lane): 64 per lane, but at
-      // least 3 waves per SIMD (196,608 lanes) while lanes keep >= 8 entries, so a small batch or
-      // segment still fills the chip instead of running a few long lanes
-      const uint64_t est = m * (nw + BV_NWR);  // entries: at most one per window of z and of z k
-      uint64_t want = kn.bucket_bal > 1 ? est / (uint64_t)kn.bucket_bal
-                                        : std::max<uint64_t>(est / 64, std::min<uint64_t>(est / 8, 196608));
-      const uint32_t cap = nk / 2;
-      uint32_t nl = (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(256, (want + 255) / 256 * 256));
-      hipLaunchKernelGGL(k_bv_bucket_bal, dim3(nl / 256), dim3(256), 0, s, pts, offs, ents, nk, nl, segV, segT);
-      hipLaunchKernelGGL(k_bv_bucket_fix, dim3(G.count * nw * BV_NB / 256), dim3(256), 0, s, offs, nk, G.count, nw, nl,
-                         segV, segT);
-    } else {
-      hipLaunchKernelGGL(k_bv_bucket, dim3(G.count * nw * (BV_NB / seg) / 256), dim3(256), 0, s, pts, offs, ents,
-                         G.count, seg, nw, segV, segT);
-    }
-  };
   {
     mark(1);
     hipLaunchKernelGGL(k_part_count, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, agg ? 1u : 0u, pcount);
     hipLaunchKernelGGL(k_part_scan, dim3(G.count * (BV_NPG / 64)), dim3(64 * SCAN_SUB), 0, s, pcount, nchunk, G, poff,
                        ptot);
     hipLaunchKernelGGL(k_part_top, dim3(1), dim3(256), 0, s, ptot, nparts, pstart);
-    if (kn.scatter_lds)
-      hipLaunchKernelGGL(k_part_scatter_lds, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, pcount, poff, pstart, G,
-                         agg ? 1u : 0u, n, 0u, tmp);
-    else
-      hipLaunchKernelGGL(k_part_scatter, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, poff, pstart, G,
-                         agg ? 1u : 0u, n, 0u, tmp);
-    if (kn.fine_lds)
-      hipLaunchKernelGGL(k_fine_sort_lds, dim3(nparts), dim3(FINE_NT), 0, s, tmp, pstart, G.count, ents, offs);
-    else
-      hipLaunchKernelGGL(k_fine_sort, dim3(nparts), dim3(FINE_NT), 0, s, tmp, pstart, G.count, ents, offs);
+    hipLaunchKernelGGL(k_part_scatter_lds, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, pcount, poff, pstart, G,
+                       agg ? 1u : 0u, n, 0u, tmp);
+    hipLaunchKernelGGL(k_fine_sort_lds, dim3(nparts), dim3(FINE_NT), 0, s, tmp, pstart, G.count, ents, offs);
     mark(2);
-    // buckets per bucket-kernel lane: one per lane while the grid is small; with many groups,
-    // a lane walks `seg` buckets and emits their running sums, so the bucket cells never go
-    // through memory and the reduction stays the size of one group's
-    buckets(n);
+    // bucket sums of the sorted entries. Equal entries per lane (at most one carry per lane):
+    // 64 per lane (MV_BUCKET_BAL > 1: that many), but at least 3 waves per SIMD (196,608 lanes)
+    // while lanes keep >= 8 entries, so a small batch still fills the chip instead of running a
+    // few long lanes
+    const uint64_t est = (uint64_t)n * (nw + BV_NWR);  // entries: at most one per window of z and of z k
+    const uint64_t want = kn.bucket_bal > 1 ? est / (uint64_t)kn.bucket_bal
+                                            : std::max<uint64_t>(est / 64, std::min<uint64_t>(est / 8, 196608));
+    const uint32_t cap = nk / 2;
+    const uint32_t nl = (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(256, (want + 255) / 256 * 256));
+    hipLaunchKernelGGL(k_bv_bucket_bal, dim3(nl / 256), dim3(256), 0, s, pts, offs, ents, nk, nl, carry, bktT);
+    hipLaunchKernelGGL(k_bv_bucket_fix, dim3(G.count * nw * BV_NB / 256), dim3(256), 0, s, offs, nk, G.count, nw, nl,
+                       carry, bktT);
   }
   if (agg) {
     hipLaunchKernelGGL(k_bv_keyacc, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, key_idx, n, n_keys, kpart);
@@ -1616,11 +1364,11 @@ hipError_t launch_msm_stage(const Knobs& kn, const uint32_t* key_idx, uint32_t n
     hipLaunchKernelGGL(k_bv_keysum, dim3(G.count), dim3(256), 0, s, keyp, n_keys, asum);
   }
   mark(3);
-  const uint4* inV = seg > 1 ? segV : nullptr;  // one bucket per segment: V = T
-  const uint4* inT = segT;
+  const uint4* inV = nullptr;  // first level: the elements are the buckets, V = T
+  const uint4* inT = bktT;
   const uint32_t rows = G.count * nw;
-  uint32_t cnt = BV_NB / seg;
-  int shift = 31 - __builtin_clz(seg);  // log2(seg)
+  uint32_t cnt = BV_NB;
+  int shift = 0;
   int pp = 0;
   while (cnt > 1) {
     const int fan = cnt >= (uint32_t)BV_FAN ? BV_FAN : (int)cnt;
@@ -1628,13 +1376,13 @@ hipError_t launch_msm_stage(const Knobs& kn, const uint32_t* key_idx, uint32_t n
     const uint32_t lanes = out * rows;
     if (lanes <= (uint32_t)kn.reduce_rows)  // small top level: a wave per element
       hipLaunchKernelGGL(k_bv_reduce_r, dim3((64 * lanes + 255) / 256), dim3(256), 0, s, inV, inT, cnt, fan, shift,
-                         rows, nw, inT == segT ? 1u : 0u, rv[pp], rt[pp]);
+                         rows, nw, inT == bktT ? 1u : 0u, rv[pp], rt[pp]);
     else if (lanes <= reduce_quad_max(kn))  // latency-bound level: four lanes per element
       hipLaunchKernelGGL(k_bv_reduce_q, dim3((4 * lanes + 255) / 256), dim3(256), 0, s, inV, inT, cnt, fan, shift,
-                         rows, nw, inT == segT ? 1u : 0u, rv[pp], rt[pp]);
+                         rows, nw, inT == bktT ? 1u : 0u, rv[pp], rt[pp]);
     else
       hipLaunchKernelGGL(k_bv_reduce, dim3((lanes + 63) / 64), dim3(64), 0, s, inV, inT, cnt, fan, shift, rows, nw,
-                         inT == segT ? 1u : 0u, rv[pp], rt[pp]);
+                         inT == bktT ? 1u : 0u, rv[pp], rt[pp]);
     inV = rv[pp];
     inT = rt[pp];
     pp ^= 1;
@@ -1679,7 +1427,7 @@ hipError_t launch_verify_batch(const Knobs& kn, const uint8_t* msg, const uint8_
   if (e != hipSuccess) return e;
   // exact fallback: re-verifies the signatures of every group whose equation failed
   // (R and A as k_bv_prep decoded them: no decompression)
-  e = launch_verify(kn, msg, sig, pk, key_idx, n, btab, vscratch, status, s, flag + 1, G.cpg * PART_CHUNK, pts,
+  e = launch_verify(msg, sig, pk, key_idx, n, btab, vscratch, status, s, flag + 1, G.cpg * PART_CHUNK, pts,
                     ca.tab && ca.aggregate ? comb_a : nullptr);
   mark(6);
   return e;

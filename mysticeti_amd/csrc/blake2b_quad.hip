@@ -26,12 +26,13 @@
 namespace mv {
 namespace b2q {
 
-#define MV_B2Q_BOUNDS __launch_bounds__(64, NS == 1 ? 4 : 3)
-template <bool DUAL, int NS>
-__global__ void MV_B2Q_BOUNDS k_b2_quad(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ off,
-                                        const uint64_t* __restrict__ len, uint32_t n, uint8_t* __restrict__ out0,
-                                        uint8_t* __restrict__ out1) {
-  quad_hash<DUAL, NS>(blockIdx.x, buf, off, len, n, out0, out1);
+// One string per quad: two interleaved strings per quad ran at the same speed on config 4 (5.16
+// vs 5.11 ms) with 60% more VGPRs, and that form is removed.
+template <bool DUAL>
+__global__ void __launch_bounds__(64, 4) k_b2_quad(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ off,
+                                                   const uint64_t* __restrict__ len, uint32_t n,
+                                                   uint8_t* __restrict__ out0, uint8_t* __restrict__ out1) {
+  quad_hash<DUAL, 1>(blockIdx.x, buf, off, len, n, out0, out1);
 }
 // the online path's form (a few waves on an idle chip): message reads hoisted out of their
 // rounds, so the LDS latency leaves the compression chain (more VGPRs, fewer waves: fine here)
@@ -41,16 +42,11 @@ __global__ void __launch_bounds__(64) k_b2_quad_lat(const uint8_t* __restrict__ 
   quad_hash<true, 1, true>(blockIdx.x, buf, off, len, n, out0, out1);
 }
 
-
 }  // namespace b2q
 }  // namespace mv
 
 namespace mvk {
 
-// strings per quad: 1 (the default: measured on config 4, 2 interleaved strings per quad ran
-// at the same speed -- 5.16 vs 5.11 ms -- with 60% more VGPRs). MV_B2Q_NS=2 selects the
-// interleaved kernel (experiments).
-static int b2q_ns(const Knobs& kn) { return kn.b2q_ns == 2 ? 2 : 1; }
 // batch-size calls: the lane-per-string kernel (blake2b_lane.hip) unless MV_B2_LANE=0
 static bool b2_lane(const Knobs& kn, uint32_t n) { return kn.b2_lane != 0 && n >= MV_BATCH_MIN; }
 
@@ -58,12 +54,8 @@ hipError_t launch_blake2b_quad(const Knobs& kn, const uint8_t* buf, const uint64
                                hipStream_t s) {
   if (n == 0) return hipSuccess;
   if (b2_lane(kn, n)) return launch_blake2b_lane(buf, off, len, n, out, s);
-  if (b2q_ns(kn) == 2)
-    hipLaunchKernelGGL((mv::b2q::k_b2_quad<false, 2>), dim3((n + 31) / 32), dim3(64), 0, s, buf, off, len, n, out,
-                       (uint8_t*)nullptr);
-  else
-    hipLaunchKernelGGL((mv::b2q::k_b2_quad<false, 1>), dim3((n + 15) / 16), dim3(64), 0, s, buf, off, len, n, out,
-                       (uint8_t*)nullptr);
+  hipLaunchKernelGGL(mv::b2q::k_b2_quad<false>, dim3((n + 15) / 16), dim3(64), 0, s, buf, off, len, n, out,
+                     (uint8_t*)nullptr);
   return hipGetLastError();
 }
 
@@ -73,11 +65,8 @@ hipError_t launch_block_hash_quad(const Knobs& kn, const uint8_t* buf, const uin
   if (b2_lane(kn, n)) return launch_block_hash_lane(buf, off, len, n, msg_out, dig_out, s);
   if (n < MV_BATCH_MIN)  // the online path (comb verify): latency form
     hipLaunchKernelGGL(mv::b2q::k_b2_quad_lat, dim3((n + 15) / 16), dim3(64), 0, s, buf, off, len, n, msg_out, dig_out);
-  else if (b2q_ns(kn) == 2)
-    hipLaunchKernelGGL((mv::b2q::k_b2_quad<true, 2>), dim3((n + 31) / 32), dim3(64), 0, s, buf, off, len, n, msg_out,
-                       dig_out);
   else
-    hipLaunchKernelGGL((mv::b2q::k_b2_quad<true, 1>), dim3((n + 15) / 16), dim3(64), 0, s, buf, off, len, n, msg_out,
+    hipLaunchKernelGGL(mv::b2q::k_b2_quad<true>, dim3((n + 15) / 16), dim3(64), 0, s, buf, off, len, n, msg_out,
                        dig_out);
   return hipGetLastError();
 }

@@ -258,7 +258,7 @@ mv_status enqueue_verify(mv_ctx* ctx, Device& dev, const uint8_t* d_msg, const u
   auto& sl = ring.slot[slot];
   // (growth retires the old buffer, which another stream's call may still read: no drain)
   HIPCHK(ctx, sl.scr.ensure(mvk::verify_scratch_bytes(n), sl.done));
-  HIPCHK(ctx, mvk::launch_verify(ctx->kn, d_msg, d_sig, d_pk, d_key_idx, n, dev.tab.btab.p, sl.scr.p, d_status, s));
+  HIPCHK(ctx, mvk::launch_verify(d_msg, d_sig, d_pk, d_key_idx, n, dev.tab.btab.p, sl.scr.p, d_status, s));
   HIPCHK(ctx, ring.mark_used(slot, s));
   return MV_OK;
 }
@@ -479,18 +479,12 @@ const KnobDef kKnobs[] = {
     {"MV_BASE_GROUPS", &mvk::Knobs::base_groups, K_INT, true},
     {"MV_NO_KEY_AGG", &mvk::Knobs::no_key_agg, K_OFF, false},
     {"MV_REDUCE_QUAD", &mvk::Knobs::reduce_quad, K_INT, false},
-    {"MV_BV_SEG", &mvk::Knobs::bv_seg, K_INT, false},
-    {"MV_B2Q_NS", &mvk::Knobs::b2q_ns, K_INT, false},
     {"MV_B2_LANE", &mvk::Knobs::b2_lane, K_ON, false},
     {"MV_COMB_QUAD", &mvk::Knobs::comb_quad, K_INT, false},
-    {"MV_INGEST_LANE", &mvk::Knobs::ingest_lane, K_OFF, false},
-    {"MV_VERIFY_OCC", &mvk::Knobs::verify_occ, K_INT, false},
     {"MV_PREP_CHAIN", &mvk::Knobs::prep_chain, K_INT, false},
     {"MV_BLK_WALK", &mvk::Knobs::blk_walk, K_ON, false},
     {"MV_BUCKET_BAL", &mvk::Knobs::bucket_bal, K_INT, false},
     {"MV_FINAL_ROWS", &mvk::Knobs::final_rows, K_ON, false},
-    {"MV_SCATTER_LDS", &mvk::Knobs::scatter_lds, K_ON, false},
-    {"MV_FINE_LDS", &mvk::Knobs::fine_lds, K_ON, false},
     {"MV_REDUCE_ROWS", &mvk::Knobs::reduce_rows, K_INT, false},
     {"MV_INDEX_TAG_BITS", &mvk::Knobs::index_tag_bits, K_INT, false},
 };

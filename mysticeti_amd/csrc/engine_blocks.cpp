@@ -122,7 +122,7 @@ mv_status enqueue_blocks(mv_ctx* ctx, Device& dev, const uint8_t* d_buf, uint64_
     for (int k = 0; k < 2; k++) HIPCHK(ctx, ax.ev[k].ensure());
     hipStream_t aux = ax.stream;
     auto parse = [&](uint32_t lo, uint32_t hi, hipStream_t st) {
-      return mvk::launch_block_parse(ctx->kn, d_buf, d_off + lo, d_len + lo, hi - lo, dev.tab.stakes.as<uint64_t>(), com.size(),
+      return mvk::launch_block_parse(d_buf, d_off + lo, d_len + lo, hi - lo, dev.tab.stakes.as<uint64_t>(), com.size(),
                                      com.epoch, com.quorum_threshold, stage, poff + lo, plen + lo, sig + 64 * (size_t)lo,
                                      kidx + lo, facts + lo, claimed + 32 * (size_t)lo, st);
     };
@@ -140,7 +140,7 @@ mv_status enqueue_blocks(mv_ctx* ctx, Device& dev, const uint8_t* d_buf, uint64_
     HIPCHK(ctx, hipStreamWaitEvent(s, ax.ev[1], 0));
     HIPCHK(ctx, hash(h, n));
   } else {
-    HIPCHK(ctx, mvk::launch_block_parse(ctx->kn, d_buf, d_off, d_len, n, dev.tab.stakes.as<uint64_t>(), com.size(), com.epoch,
+    HIPCHK(ctx, mvk::launch_block_parse(d_buf, d_off, d_len, n, dev.tab.stakes.as<uint64_t>(), com.size(), com.epoch,
                                         com.quorum_threshold, stage, poff, plen, sig, kidx, facts, claimed, s));
     HIPCHK(ctx, mark(1));
     if (split)  // the hash, and beside it on workgroups of their own the signature-only terms

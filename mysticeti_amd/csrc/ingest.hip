@@ -1,6 +1,6 @@
 // Device-side StatementBlock ingest for gfx950: bincode
 // Data<StatementBlock> bytes resident in HBM -> the signed pre-image P || sig, staged for
-// k_block_hash, plus the facts StatementBlock::verify checks; one block per lane.
+// k_block_hash, plus the facts StatementBlock::verify checks; one wave per block.
 // k_block_verdict folds the digest comparison, the signature verdict and those facts into
 // one status in the reference's error order (types.rs:315-376).
 //
@@ -27,22 +27,9 @@
 
 namespace mv {
 
-// Lane per block over global memory (the reference implementation of the ingest; the
-// product launches k_block_ingest, which falls back to ingest_lane for oversize blocks).
-__global__ void __launch_bounds__(256) k_block_parse(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ off,
-                                                     const uint64_t* __restrict__ len, uint32_t n, CommitteeView cv,
-                                                     IngestOut io) {
-  __shared__ uint32_t seen[16][256];  // per-lane authority bitmap, [word][lane]
-  const uint32_t t = threadIdx.x;
-  const uint32_t i = blockIdx.x * 256 + t;
-#pragma unroll
-  for (int k = 0; k < 16; k++) seen[k][t] = 0;
-  if (i >= n) return;
-  ingest_lane(buf, off[i], len[i], i, cv, io, &seen[0][t], 256);
-}
-
 // ---------------------------------------------------------------- wave per block
-// k_block_ingest: one 64-lane workgroup per block (ingest_dev.h's ingest_block).
+// k_block_ingest: one 64-lane workgroup per block (ingest_dev.h's ingest_block, which hands a
+// block over its staging window to the one-lane function ingest_lane).
 __global__ void __launch_bounds__(64) k_block_ingest(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ off,
                                                      const uint64_t* __restrict__ len, uint32_t n, CommitteeView cv,
                                                      IngestOut io) {
@@ -82,18 +69,16 @@ __global__ void __launch_bounds__(256) k_block_verdict(const uint32_t* __restric
 // ---------------------------------------------------------------- launchers
 namespace mvk {
 
-hipError_t launch_block_parse(const Knobs& kn, const uint8_t* buf, const uint64_t* off, const uint64_t* len, uint32_t n,
+hipError_t launch_block_parse(const uint8_t* buf, const uint64_t* off, const uint64_t* len, uint32_t n,
                               const uint64_t* stakes, uint32_t n_auth, uint64_t epoch, uint64_t quorum_thr,
                               uint8_t* stage, uint64_t* pre_off, uint64_t* pre_len, uint8_t* sig, uint32_t* key_idx,
                               uint32_t* facts, uint8_t* claimed, hipStream_t s) {
   if (n == 0) return hipSuccess;
   const mv::CommitteeView cv{stakes, n_auth, epoch, quorum_thr};
   const mv::IngestOut io{stage, pre_off, pre_len, sig, key_idx, facts, claimed};
-  if (kn.ingest_lane)  // A/B (MV_INGEST_LANE=1): the lane-per-block kernel
-    hipLaunchKernelGGL(mv::k_block_parse, dim3((n + 255) / 256), dim3(256), 0, s, buf, off, len, n, cv, io);
-  else  // (capping its workgroups per CU with padded LDS, to leave room for the other stream's
-        // kernels, measured slower: 79 vs 103 M config-4 blocks/s, profiles/r03/ab/)
-    hipLaunchKernelGGL(mv::k_block_ingest, dim3(n), dim3(64), 0, s, buf, off, len, n, cv, io);
+  // (capping its workgroups per CU with padded LDS, to leave room for the other stream's
+  // kernels, measured slower: 79 vs 103 M config-4 blocks/s, profiles/r03/ab/)
+  hipLaunchKernelGGL(mv::k_block_ingest, dim3(n), dim3(64), 0, s, buf, off, len, n, cv, io);
   return hipGetLastError();
 }
 

@@ -118,7 +118,8 @@ struct CommitteeView {
   uint64_t epoch, quorum_thr;
 };
 
-// Block i = buf[o .. o + L), one lane, straight from global memory. P || sig (then 8 zero
+// Block i = buf[o .. o + L), one lane, straight from global memory (no kernel of its own:
+// ingest_block calls it for a block over its LDS window). P || sig (then 8 zero
 // bytes) is written at stage + round_up(o, 8), which stays inside the block's own span
 // because the bincode is at least |P| + 128 bytes long; writes happen only after the bytes
 // they come from were read, so a malformed block never writes outside its span either.
@@ -287,8 +288,9 @@ MV_DEV void ingest_lane(const uint8_t* buf, uint64_t o, uint64_t L, uint32_t i, 
 // variable-size statements are located 64 at a time by lane 0 walking their headers, then
 // transcoded one per lane (Share payloads copied by the whole wave); the pre-image is built
 // in LDS and written to the stage with coalesced stores. Blocks that do not fit the LDS
-// window take ingest_lane on lane 0. The rules are ingest_lane's (and block_codec.cpp's);
-// tests/test_gpu_ingest.py holds the two kernels and the host codec to identical results.
+// window take the one-lane function ingest_lane on lane 0. The rules are ingest_lane's (and
+// block_codec.cpp's); tests/test_gpu_ingest.py holds every ingest form and the host codec to
+// identical results.
 constexpr uint32_t IG_WIN = 10240;  // LDS window per block, bytes
 constexpr uint32_t IG_CHUNK = 64;   // statements located per walk
 

@@ -44,17 +44,11 @@ struct Knobs {
   // kernel forms (the launchers)
   int64_t no_key_agg = 0;                // MV_NO_KEY_AGG: committee A terms as bucket entries
   int64_t reduce_quad = 16384;           // MV_REDUCE_QUAD: quad-reduce threshold
-  int64_t bv_seg = -1;                   // MV_BV_SEG: bucket segment length (-1: measured best)
-  int64_t b2q_ns = 0;                    // MV_B2Q_NS: strings per quad in k_b2_quad (2: interleaved)
   int64_t b2_lane = 1;                   // MV_B2_LANE: batch-size BLAKE2b one lane per string
   int64_t comb_quad = -1;                // MV_COMB_QUAD: force k_verify_comb16 (1) / k_verify_comb (0)
-  int64_t ingest_lane = 0;               // MV_INGEST_LANE: the lane-per-block ingest kernel
-  int64_t verify_occ = 2;                // MV_VERIFY_OCC: k_verify's waves per SIMD (1, 2, 3)
   int64_t reduce_rows = 1024;            // MV_REDUCE_ROWS: reduction levels of <= this many elements a wave each (0: none)
-  int64_t fine_lds = 1;                  // MV_FINE_LDS: the fine sort staged in registers + LDS (coalesced stores)
-  int64_t scatter_lds = 1;               // MV_SCATTER_LDS: the partition scatter staged in LDS (coalesced stores)
   int64_t final_rows = 1;                // MV_FINAL_ROWS: k_bv_final's Horner with one DPP row per coordinate
-  int64_t bucket_bal = 1;                // MV_BUCKET_BAL: equal entries per bucket-kernel lane (>1: entries per lane)
+  int64_t bucket_bal = 1;                // MV_BUCKET_BAL: entries per bucket-kernel lane (<= 1: 64, with the chip-filling floor)
   int64_t prep_chain = 1;                // MV_PREP_CHAIN: a batch's k_bv_prep starts after the previous batch's
                                          // (1: on the engine's streams; 2: on callers' streams too)
   int64_t blk_walk = 1;                  // MV_BLK_WALK: batch-size block calls in one pass over the bincode (k_block_walk); 0: staged pre-image
@@ -65,10 +59,9 @@ struct Knobs {
 size_t verify_scratch_bytes(uint32_t n);
 size_t btable_bytes();
 hipError_t launch_btable_init(void* d_btab, hipStream_t s);
-hipError_t launch_verify(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* key_idx,
-                         uint32_t n, const void* btab, void* scratch, uint8_t* status, hipStream_t s,
-                         const uint32_t* skip = nullptr, uint32_t skip_group = 0, const void* prep_pts = nullptr,
-                         const void* prep_comb = nullptr);
+hipError_t launch_verify(const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* key_idx, uint32_t n,
+                         const void* btab, void* scratch, uint8_t* status, hipStream_t s, const uint32_t* skip = nullptr,
+                         uint32_t skip_group = 0, const void* prep_pts = nullptr, const void* prep_comb = nullptr);
 // skip (optional, device): per-group flags; the signatures of group g = i / skip_group
 // (skip_group a multiple of 256; 0 = one group) are not verified when skip[g] != 0.
 // prep_pts (the batch path's fallback): R and A as k_bv_prep decoded them (A from the comb
@@ -315,7 +308,7 @@ hipError_t launch_comb_post(const uint8_t* msg, const uint8_t* sig, const uint8_
                             const void* sbuf, const uint8_t* qflags, uint8_t* status, hipStream_t s,
                             const BlockVerdictOut* bv = nullptr);
 // ingest.hip: device-side bincode parse + pre-image staging, and the final block verdict
-hipError_t launch_block_parse(const Knobs& kn, const uint8_t* buf, const uint64_t* off, const uint64_t* len, uint32_t n,
+hipError_t launch_block_parse(const uint8_t* buf, const uint64_t* off, const uint64_t* len, uint32_t n,
                               const uint64_t* stakes, uint32_t n_auth, uint64_t epoch, uint64_t quorum_thr,
                               uint8_t* stage, uint64_t* pre_off, uint64_t* pre_len, uint8_t* sig, uint32_t* key_idx,
                               uint32_t* facts, uint8_t* claimed, hipStream_t s);

@@ -145,15 +145,14 @@ struct PrepView {
 };
 
 // One signature per lane. pk rows are read at key_idx[i] when key_idx != nullptr.
-// MINW = minimum waves per SIMD (2 -> <= 256 VGPRs, 1 -> <= 512).
+// Two waves per SIMD (<= 256 VGPRs): occupancies 1 and 3 were measured no faster and removed.
 //
 // Checks [8]([e]B - [c]A - [d]R) == O with e = d*s mod l, (c, d) = sc_halfsize(k),
 // which holds iff the ZIP-215 equation [8]([s]B - [k]A - R) == O does (see
 // sc_halfsize). e's signed radix-256 digits 0..15 go against [j]B at the even 4-bit
 // windows, digits 16..31 against [j](2^124 B) at the odd ones, so every one of the
 // 32 windows does 4 doublings and three additions (A, R, B or 2^124 B).
-template <int MINW>
-__global__ void __launch_bounds__(256, MINW)
+__global__ void __launch_bounds__(256, 2)
     k_verify(const uint8_t* __restrict__ msg, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ pk,
              const uint32_t* __restrict__ key_idx, uint32_t n, const uint4* __restrict__ btab_g,
              uint4* __restrict__ scratch, uint8_t* __restrict__ status, const uint32_t* __restrict__ skip,
@@ -811,28 +810,19 @@ size_t verify_scratch_bytes(uint32_t n) {
   size_t waves = (size_t)((n + 255) / 256) * 4;  // every wave of the 256-thread grid owns a slot
   return waves * mv::WAVE_QUADS * 64 * sizeof(uint4);
 }
-// MV_VERIFY_OCC (A/B): k_verify's waves per SIMD, 1, 2 (default) or 3
-static int verify_variant(const Knobs& kn) { return kn.verify_occ == 1 || kn.verify_occ == 3 ? (int)kn.verify_occ : 2; }
 size_t btable_bytes() { return 2 * mv::BT_TABLE * sizeof(uint4); }
 
 hipError_t launch_btable_init(void* d_btab, hipStream_t s) {
   hipLaunchKernelGGL(mv::k_btable_init, dim3(2), dim3(256), 0, s, (uint4*)d_btab);
   return hipGetLastError();
 }
-hipError_t launch_verify(const Knobs& kn, const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* key_idx,
-                         uint32_t n, const void* btab, void* scratch, uint8_t* status, hipStream_t s,
-                         const uint32_t* skip, uint32_t skip_group, const void* prep_pts, const void* prep_comb) {
+hipError_t launch_verify(const uint8_t* msg, const uint8_t* sig, const uint8_t* pk, const uint32_t* key_idx, uint32_t n,
+                         const void* btab, void* scratch, uint8_t* status, hipStream_t s, const uint32_t* skip,
+                         uint32_t skip_group, const void* prep_pts, const void* prep_comb) {
   if (n == 0) return hipSuccess;
   const mv::PrepView pv{static_cast<const uint4*>(prep_pts), n, static_cast<const uint4*>(prep_comb)};
-  if (verify_variant(kn) == 1)
-    hipLaunchKernelGGL(mv::k_verify<1>, dim3((n + 255) / 256), dim3(256), 0, s, msg, sig, pk, key_idx, n,
-                       (const uint4*)btab, (uint4*)scratch, status, skip, skip_group, pv);
-  else if (verify_variant(kn) == 3)
-    hipLaunchKernelGGL(mv::k_verify<3>, dim3((n + 255) / 256), dim3(256), 0, s, msg, sig, pk, key_idx, n,
-                       (const uint4*)btab, (uint4*)scratch, status, skip, skip_group, pv);
-  else
-    hipLaunchKernelGGL(mv::k_verify<2>, dim3((n + 255) / 256), dim3(256), 0, s, msg, sig, pk, key_idx, n,
-                       (const uint4*)btab, (uint4*)scratch, status, skip, skip_group, pv);
+  hipLaunchKernelGGL(mv::k_verify, dim3((n + 255) / 256), dim3(256), 0, s, msg, sig, pk, key_idx, n,
+                     (const uint4*)btab, (uint4*)scratch, status, skip, skip_group, pv);
   return hipGetLastError();
 }
 hipError_t launch_sign(const uint8_t* seed, const uint8_t* msg, uint32_t n, const void* btab, uint8_t* pk,

@@ -15,7 +15,7 @@ constexpr int BT_TABLE = BT_ENTRIES * BT_QUADS;  // uint4 per fixed-base table
 constexpr int AT_ENTRIES = 9;    // [0..8](-A), [0..8](-R)
 constexpr int AT_QUADS = 9;
 constexpr int AT_TABLE = AT_ENTRIES * AT_QUADS;  // uint4 per lane per variable-base table
-// batch-path points (k_bv_prep -> k_bv_bucket, and the fallback): affine precomp, 27 limb
+// batch-path points (k_bv_prep -> k_bv_bucket_bal, and the fallback): affine precomp, 27 limb
 // words padded to one 128-B line, so a bucket's gather touches one line (112-B packed
 // records measured the same: 1.67 vs 1.68 ms per 2^20 batch)
 constexpr int PT_QUADS = 8;

@@ -450,13 +450,13 @@ def test_two_concurrent_pinned_callers(committee):
                 assert (st == data[c][4]).all(), np.nonzero(st != data[c][4])[0][:8]
 
 
-@pytest.mark.parametrize("bal", [0, 1, 7, 200])
+@pytest.mark.parametrize("bal", [1, 7, 200])
 @pytest.mark.parametrize("groups", [0, 5])
 def test_bucket_forms_agree(engine, opts, bal, groups):
-    """Both bucket kernels (one lane per bucket: MV_BUCKET_BAL=0; equal entries per lane: 1 =
-    64 per lane, or 7 / 200 entries so that lanes split buckets many ways or hold many
-    buckets) give equations that hold on valid batches and fail exactly where a signature is
-    bad, with and without sub-batch equations."""
+    """The bucket kernel at every lane length (equal entries per lane, MV_BUCKET_BAL: 1 = 64 per
+    lane, or 7 / 200 entries so that lanes split buckets many ways or hold many buckets) gives
+    equations that hold on valid batches and fail exactly where a signature is bad, with and
+    without sub-batch equations."""
     opts("MV_BUCKET_BAL", bal)
     n = 9000
     msg, sig, pk = signed(engine, n, 77)
@@ -472,15 +472,13 @@ def test_bucket_forms_agree(engine, opts, bal, groups):
         engine.set_batch_groups(0)
 
 
-@pytest.mark.parametrize("bal", [1, 0])
-def test_streamed_small_copy_chunks(engine, opts, bal):
+def test_streamed_small_copy_chunks(engine, opts):
     """Pinned inputs in 4,096-signature copy chunks (MV_STREAM_CHUNK_LOG2=12: k_bv_prep runs
-    chunk by chunk as the copies land), with both bucket kernels: the equation holds on a valid
-    call without a fallback, and bad signatures at chunk edges come back exact."""
-    for name, v in (("MV_STREAM_CHUNK_LOG2", 12), ("MV_BUCKET_BAL", bal)):
-        opts(name, v)
+    chunk by chunk as the copies land): the equation holds on a valid call without a fallback,
+    and bad signatures at chunk edges come back exact."""
+    opts("MV_STREAM_CHUNK_LOG2", 12)
     n = 9 * M.BATCH_MIN + 333
-    msg, sig, pk = signed(engine, n, 91 + bal)
+    msg, sig, pk = signed(engine, n, 92)
 
     def pin(a):
         h = engine.host_empty(a.shape, a.dtype)

@@ -1,5 +1,5 @@
-"""GPU: the batch path's stages after the preparation (batch.hip: k_part_*, k_fine_sort*,
-k_bv_bucket*, k_bv_key*, k_bv_reduce*, k_bv_final) against the plain model of tests/msm_model.py.
+"""GPU: the batch path's stages after the preparation (batch.hip: k_part_*, k_fine_sort_lds,
+k_bv_bucket_*, k_bv_key*, k_bv_reduce*, k_bv_final) against the plain model of tests/msm_model.py.
 
 The verdict tests see these stages through two observations only: a valid batch passes without a
 fallback, and a batch with a bad signature comes back exact. A wrong sum shows there as a silent
@@ -147,10 +147,8 @@ def test_chosen_scalars(engine, name):
         check(engine, rows, cols, expect=[1, 1, 1])
 
 
-FORMS = [("MV_BUCKET_BAL", 0), ("MV_BUCKET_BAL", 1), ("MV_BUCKET_BAL", 8), ("MV_BV_SEG", 1), ("MV_BV_SEG", 4),
-         ("MV_FINE_LDS", 0), ("MV_FINE_LDS", 1), ("MV_SCATTER_LDS", 0), ("MV_SCATTER_LDS", 1), ("MV_REDUCE_QUAD", 0),
-         ("MV_REDUCE_QUAD", None), ("MV_REDUCE_ROWS", 0), ("MV_REDUCE_ROWS", None), ("MV_FINAL_ROWS", 0),
-         ("MV_FINAL_ROWS", 1)]
+FORMS = [("MV_BUCKET_BAL", 1), ("MV_BUCKET_BAL", 8), ("MV_REDUCE_QUAD", 0), ("MV_REDUCE_QUAD", None),
+         ("MV_REDUCE_ROWS", 0), ("MV_REDUCE_ROWS", None), ("MV_FINAL_ROWS", 0), ("MV_FINAL_ROWS", 1)]
 
 
 @pytest.mark.parametrize("knob,value", FORMS, ids=[f"{k}={'default' if v is None else v}" for k, v in FORMS])

@@ -558,3 +558,23 @@ def test_live_resources_is_read_only(engine):
     with pytest.raises(M.MvError, match=r"failed \(-1\).*read-only"):  # MV_E_INVALID_ARG
         engine.set_option("MV_LIVE_RESOURCES", 0)
     assert engine.get_option("MV_LIVE_RESOURCES") == v
+
+
+def test_removed_kernel_form_switches_are_unknown(engine, opts):
+    """The switches of the kernel forms that were removed are no options any more:
+    mv_set_option and mv_get_option refuse each name as unknown. MV_BUCKET_BAL below 1 is taken as
+    1: the value is stored as given and the stages give what they give at 1."""
+    for name in ("MV_SCATTER_LDS", "MV_FINE_LDS", "MV_BV_SEG", "MV_B2Q_NS", "MV_INGEST_LANE", "MV_VERIFY_OCC"):
+        with pytest.raises(M.MvError, match=r"failed \(-1\).*unknown option " + name):  # MV_E_INVALID_ARG
+            engine.set_option(name, 1)
+        with pytest.raises(M.MvError, match=r"failed \(-1\).*unknown option " + name):
+            engine.get_option(name)
+    import msm_model as MM
+
+    rows = MM.Rows([3 + (i << 70) for i in range(300)], [(5 + i) << 200 for i in range(300)])
+    cols = rows.balanced()
+    for v in (1, 0, -3):  # (the sums are compared as points: the entry order inside a bucket is not fixed)
+        opts("MV_BUCKET_BAL", v)
+        assert engine.get_option("MV_BUCKET_BAL") == v
+        out = engine.batch_msm(rows.scal, rows.pts, cols)
+        assert out.flags == [1] and all(MM.row_equals(out.win[0, w], rows.W[0][w]) for w in range(16)), v
