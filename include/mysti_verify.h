@@ -48,6 +48,9 @@
  *                          (net_sync.rs:325-336, core_thread/spawned.rs:140-150) ahead of verify, and after it the
  *                          include lookups of BlockManager::add_blocks (block_manager.rs:48-136) whose result the
  *                          syncer requests from peers (net_sync.rs:388-398)
+ *   mv_connect_blocks      mv_accept_blocks and the suspend / unlock cascade of add_blocks (block_manager.rs:102-131)
+ *                          over a store of suspended blocks in device memory: the blocks the core may process,
+ *                          in a causal order
  *
  * Conventions
  *   - The caller owns every buffer passed in and out; they must stay valid for the call.
@@ -130,6 +133,9 @@ typedef int32_t mv_status;
 #define MV_REF_WANTED 1 /* an accepted block includes it and it has not arrived: a key of block_references_waiting
                            that is not pending, i.e. BlockManager::missing (block_manager.rs:90-97) */
 #define MV_REF_HAVE 2   /* stored or pending: BlockManager::exists_or_pending (block_manager.rs:142-144) */
+#define MV_REF_STORED 3 /* in the store: the block and its whole causal history have been accepted
+                           (BlockStore::block_exists). Only mv_connect_blocks and a caller's seeding produce it;
+                           every call that asks for HAVE means HAVE or STORED */
 
 /* per-block outcome of mv_accept_blocks */
 #define MV_ACC_REJECTED 0 /* its own MV_BLOCK_* is not OK */
@@ -138,6 +144,8 @@ typedef int32_t mv_status;
 #define MV_ACC_DUP 3      /* accepted, but a block of a lower index has the same reference (block_manager.rs:68-72) */
 #define MV_ACC_DROPPED 4  /* OK itself, but a block of its group was rejected: process_blocks returned before
                              add_blocks (net_sync.rs:352-361) */
+#define MV_ACC_SUSPENDED 5 /* mv_connect_blocks only: accepted as MV_ACC_NEW, but an include is not stored yet:
+                              the block waits in blocks_pending (block_manager.rs:102-110) */
 
 /* mv_config.flags */
 #define MV_FLAG_NO_BATCH 1u /* host-buffer verify: never use the batch (random linear combination) path */
@@ -390,7 +398,7 @@ mv_status mv_verify_frames(mv_ctx* ctx, const uint8_t* buf, const uint64_t* soff
  * 1/2 (the entries are rehashed on the device). Never shrinks. mv_index_clear empties it. */
 mv_status mv_index_reserve(mv_ctx* ctx, uint64_t entries);
 mv_status mv_index_clear(mv_ctx* ctx);
-/* out[0] HAVE entries, out[1] WANTED entries, out[2] the capacity in entries, out[3] rebuilds so far,
+/* out[0] HAVE entries (MV_REF_STORED ones among them), out[1] WANTED entries, out[2] the capacity in entries, out[3] rebuilds so far,
  * out[4] the longest probe (slots examined) of any insert or lookup since the last clear. */
 mv_status mv_index_stats(mv_ctx* ctx, uint64_t* out /* 5 */);
 /* Raises n references to `state` (MV_REF_WANTED or MV_REF_HAVE): absent ones are entered, a WANTED one
@@ -399,6 +407,12 @@ mv_status mv_index_stats(mv_ctx* ctx, uint64_t* out /* 5 */);
  * too. Grows the index as needed. */
 mv_status mv_index_insert(mv_ctx* ctx, const uint64_t* refs /* n x 6 */, uint64_t n, uint32_t state,
                           uint8_t* prior /* n, may be NULL */);
+/* mv_index_insert towards MV_REF_STORED (which mv_index_insert itself goes on refusing): the
+ * references of blocks that are in the store -- the genesis blocks, the blocks of a replayed WAL, the
+ * caller's own proposed block. A caller that wants mv_connect_blocks to release anything seeds these
+ * as STORED, not HAVE: a block connects only when every include is STORED. */
+mv_status mv_index_insert_stored(mv_ctx* ctx, const uint64_t* refs /* n x 6 */, uint64_t n,
+                                 uint8_t* prior /* n, may be NULL */);
 /* state[i] = MV_REF_* of refs[i] (BlockStore::block_exists || blocks_pending.contains_key for HAVE,
  * block_manager.rs:68-69). */
 mv_status mv_index_lookup(mv_ctx* ctx, const uint64_t* refs /* n x 6 */, uint64_t n, uint8_t* state /* n */);
@@ -429,11 +443,49 @@ mv_status mv_index_wanted(mv_ctx* ctx, uint64_t* refs /* cap x 6 */, uint64_t ca
  * *n_missing is the total; nothing is written past min(*n_missing, cap_missing) rows. Page-locked
  * (mv_host_alloc), ordered, disjoint blocks are DMAd in place as mv_verify_blocks does; others are
  * packed. Grows the index as needed. The suspend / unlock cascade of add_blocks (blocks_pending,
- * :102-131) and the WAL write stay with the caller. Requires mv_set_committee. */
+ * :102-131) is mv_connect_blocks'; with this call it and the WAL write stay with the caller.
+ * Requires mv_set_committee. */
 mv_status mv_accept_blocks(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off, const uint64_t* len,
                            const uint64_t* grp /* n, may be NULL */, uint32_t n, uint8_t* blk_status /* n */,
                            uint8_t* blk_state /* n */, uint64_t* missing /* cap_missing x 6 */, uint64_t cap_missing,
                            uint64_t* n_missing);
+/* mv_accept_blocks and the suspend / unlock cascade of add_blocks (block_manager.rs:102-131): the
+ * whole of BlockManager::add_blocks but the block bodies and the WAL write. Steps 1-5 are those of
+ * mv_accept_blocks. Then:
+ *  6. Every NEW block joins the context's suspended-block store (device memory: its own reference,
+ *     its includes, its arrival position) in block order, and the store is swept level by level:
+ *     S_0 is the set of MV_REF_STORED references after step 5; level l connects every suspended
+ *     block that is not in S_l and whose includes are all in S_l (a block without includes
+ *     connects); their references rise to MV_REF_STORED, and S_l+1 is S_l with them. The sweep ends
+ *     at the first level that connects nothing. Connected blocks leave the store; what stays is
+ *     blocks_pending. (An include of a suspended block is a key of block_references_waiting exactly
+ *     while it is not stored, so this is the unlock test of :120-123, and the result is add_blocks'
+ *     newly_blocks_processed as a set.)
+ * connected row k is 8 words: 0-5 the reference, 6 the block's index in this call (UINT64_MAX: an
+ * earlier call suspended it), 7 its level. Rows are ordered by level and, within a level, by
+ * arrival: blocks suspended by earlier calls first, in the order they were suspended, then this
+ * call's by index. The order is causal: every include of a row was STORED before the call or stands
+ * in an earlier row. *n_connected is the total; nothing is written past min(*n_connected,
+ * cap_connected) rows, and the states rise in full whatever the cap.
+ * blk_state: a NEW block that connected stays MV_ACC_NEW, one that was parked is MV_ACC_SUSPENDED.
+ * n = 0 is a sweep alone, for after the caller raised references with mv_index_insert_stored.
+ * A context whose genesis references were seeded as MV_REF_HAVE never connects anything.
+ * Grows the index and the store as needed. Results do not depend on MV_INDEX_TAG_BITS.
+ * After an error from this call (or its device-buffer variant) other than MV_E_INDEX_FULL and
+ * MV_E_INVALID_ARG, which leave index and store as they were, references of the call's blocks may
+ * be MV_REF_HAVE without a record in the store: such blocks would be KNOWN from then on and never
+ * connect. The caller then empties both with mv_index_clear and seeds again. */
+mv_status mv_connect_blocks(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off, const uint64_t* len,
+                            const uint64_t* grp /* n, may be NULL */, uint32_t n, uint8_t* blk_status /* n */,
+                            uint8_t* blk_state /* n */, uint64_t* missing /* cap_missing x 6 */, uint64_t cap_missing,
+                            uint64_t* n_missing, uint64_t* connected /* cap_connected x 8 */, uint64_t cap_connected,
+                            uint64_t* n_connected);
+/* Room in the suspended-block store for `blocks` blocks with `includes` includes in all (never
+ * shrinks); mv_index_clear empties the store, mv_destroy frees it. */
+mv_status mv_pending_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t includes);
+/* out[0] MV_REF_STORED entries, out[1] suspended blocks, out[2] their includes, out[3] the levels
+ * (that connected something) of the last connect call. */
+mv_status mv_pending_stats(mv_ctx* ctx, uint64_t* out /* 4 */);
 
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
@@ -509,13 +561,24 @@ mv_status mv_dev_accept_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, ui
                                uint8_t* d_blk_status, uint8_t* d_blk_state, uint64_t* d_missing, uint64_t cap_missing,
                                uint64_t* n_missing, void* stream);
 /* mv_index_insert of n references that lie in device memory at a stride: reference i is the six words
- * at d_words + i * stride_words (stride_words >= 6). A replay's rows go in straight from HBM
+ * at d_words + i * stride_words (stride_words >= 6); `state` may also be MV_REF_STORED (a replay's
+ * rows are stored blocks: a caller of mv_connect_blocks seeds them so). A replay's rows go in straight from HBM
  * (d_blk_rows + 3, stride 10: BlockStore::open's add_unloaded, block_store.rs:398-404). Enqueue only.
  * It cannot grow the index: MV_E_INDEX_FULL, with the index unchanged, when n more entries may not
  * fit. A tag collision (probability 2^-64 per pair at the default MV_INDEX_TAG_BITS) takes more
  * rounds than the call enqueues ahead; it then surfaces as MV_E_HIP from the next index call. */
 mv_status mv_dev_index_insert(mv_ctx* ctx, int device, const uint64_t* d_words, uint64_t stride_words, uint64_t n,
                               uint32_t state, void* stream);
+/* mv_connect_blocks on blocks already in HBM, as mv_dev_accept_blocks is to mv_accept_blocks: every
+ * array is device memory, *n_missing and *n_connected are written on the host, `stream` is
+ * synchronised. It can grow neither the index nor the suspended-block store: MV_E_INDEX_FULL, decided
+ * before the first insert with index and store unchanged, when the blocks that are not KNOWN plus the
+ * includes of the OK ones may not fit the index (mv_index_reserve) or the store (mv_pending_reserve). */
+mv_status mv_dev_connect_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, uint64_t buf_bytes,
+                                const uint64_t* d_off, const uint64_t* d_len, const uint64_t* d_grp, uint32_t n,
+                                uint8_t* d_blk_status, uint8_t* d_blk_state, uint64_t* d_missing, uint64_t cap_missing,
+                                uint64_t* n_missing, uint64_t* d_connected, uint64_t cap_connected,
+                                uint64_t* n_connected, void* stream);
 /* crc32fast::hash of n strings of device buffer d_buf at d_off/d_len (device arrays) -> d_out. Enqueue only. */
 mv_status mv_dev_crc32(mv_ctx* ctx, int device, const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len,
                        uint32_t n, uint32_t* d_out, void* stream);

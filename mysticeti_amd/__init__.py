@@ -30,7 +30,10 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.accept_blocks     process_blocks with its `processed` skip ahead of verify (net_sync.rs:325-336)
                            and the include lookups of BlockManager::add_blocks after it
                            (block_manager.rs:48-136): per-block outcomes and the missing references
-  Engine.dev_accept_blocks, Engine.dev_index_insert
+  Engine.connect_blocks    accept_blocks and the suspend / unlock cascade of add_blocks
+                           (block_manager.rs:102-131) over a store of suspended blocks in device memory:
+                           the blocks the core may process, in a causal order
+  Engine.dev_accept_blocks, Engine.dev_connect_blocks, Engine.dev_index_insert
                            the same on buffers already in HBM (a replay's rows go in at a stride)
   frame_messages           the frame and message walk alone, on the host, for one stream
   crypto.*                 thin reference-named wrappers (BlockDigest, PublicKey, Signer, ...)
@@ -68,6 +71,7 @@ EXPORTS = [
     "mv_frame_blocks", "mv_frame_messages", "mv_verify_frames", "mv_dev_verify_frames",
     "mv_index_reserve", "mv_index_clear", "mv_index_stats", "mv_index_insert", "mv_index_lookup", "mv_index_wanted",
     "mv_accept_blocks", "mv_dev_accept_blocks", "mv_dev_index_insert",
+    "mv_index_insert_stored", "mv_connect_blocks", "mv_dev_connect_blocks", "mv_pending_reserve", "mv_pending_stats",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
@@ -80,9 +84,10 @@ MSG_STATUS = ["OK", "DECODE_ERROR", "BLOCK_REJECTED", "TOO_MANY_REQUESTED", "NOT
 MSG_OK, MSG_DECODE_ERROR, MSG_BLOCK_REJECTED, MSG_TOO_MANY_REQUESTED, MSG_NOT_REACHED, MSG_BAD_SIZE = range(6)
 MSG_NONE = 0xFFFFFFFF
 # the index of block references: states of a reference, per-block outcomes of accept_blocks
-REF_ABSENT, REF_WANTED, REF_HAVE = 0, 1, 2
-ACC_STATE = ["REJECTED", "NEW", "KNOWN", "DUP", "DROPPED"]
-ACC_REJECTED, ACC_NEW, ACC_KNOWN, ACC_DUP, ACC_DROPPED = range(5)
+REF_ABSENT, REF_WANTED, REF_HAVE, REF_STORED = 0, 1, 2, 3
+ACC_STATE = ["REJECTED", "NEW", "KNOWN", "DUP", "DROPPED", "SUSPENDED"]
+ACC_REJECTED, ACC_NEW, ACC_KNOWN, ACC_DUP, ACC_DROPPED, ACC_SUSPENDED = range(6)
+CONNECT_EARLIER = 0xFFFFFFFFFFFFFFFF  # word 6 of a connected row: an earlier call suspended the block
 E_INDEX_FULL = -6
 WAL_MAP_BITS, WAL_MAP_BITS_TEST = 24, 16  # wal.rs:95-103
 # batch path stages, the block pipeline's, the WAL replay's (mv_stage_times order, MV_NSTAGES)
@@ -176,6 +181,11 @@ def load_library(path: str = LIB_PATH):
     lib.mv_accept_blocks.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, u64, vp]
     lib.mv_dev_accept_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp]
     lib.mv_dev_index_insert.argtypes = [vp, ctypes.c_int, vp, u64, u64, u32, vp]
+    lib.mv_index_insert_stored.argtypes = [vp, vp, u64, vp]
+    lib.mv_connect_blocks.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp, u64, vp]
+    lib.mv_dev_connect_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp, u64, vp, vp]
+    lib.mv_pending_reserve.argtypes = [vp, u64, u64]
+    lib.mv_pending_stats.argtypes = [vp, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     lib.mv_host_free.argtypes = [vp, vp]
     lib.mv_host_free.restype = None
@@ -627,6 +637,7 @@ class Engine:
 
     def index_clear(self):
         self._check(self.lib.mv_index_clear(self.ctx), "mv_index_clear")
+        self._suspended = 0
 
     def index_stats(self) -> "IndexStats":
         out = np.zeros(5, dtype=np.uint64)
@@ -641,8 +652,17 @@ class Engine:
         self._check(self.lib.mv_index_insert(self.ctx, _p(r), r.shape[0], int(state), _p(prior)), "mv_index_insert")
         return prior
 
+    def index_insert_stored(self, refs) -> np.ndarray:
+        """Raises references to REF_STORED (mv_index_insert_stored): blocks that are in the store --
+        genesis, a replayed WAL, an own proposal. Returns the state each had before the call."""
+        r = ref_words(refs)
+        prior = np.zeros(r.shape[0], dtype=np.uint8)
+        self._check(self.lib.mv_index_insert_stored(self.ctx, _p(r), r.shape[0], _p(prior)), "mv_index_insert_stored")
+        return prior
+
     def index_lookup(self, refs) -> np.ndarray:
-        """REF_* of every reference: REF_HAVE is BlockManager::exists_or_pending."""
+        """REF_* of every reference: REF_HAVE or REF_STORED is BlockManager::exists_or_pending,
+        REF_STORED BlockStore::block_exists."""
         r = ref_words(refs)
         st = np.zeros(r.shape[0], dtype=np.uint8)
         self._check(self.lib.mv_index_lookup(self.ctx, _p(r), r.shape[0], _p(st)), "mv_index_lookup")
@@ -703,6 +723,65 @@ class Engine:
             d_missing.shape[0] if d_missing is not None else 0, ctypes.byref(nm), vp(stream_handle or None)),
             "mv_dev_accept_blocks")
         return int(nm.value)
+
+    def connect_blocks(self, blocks: Sequence[bytes] = (), groups=None, cap_missing: Optional[int] = None,
+                       cap_connected: Optional[int] = None, connected_out: Optional[np.ndarray] = None) -> "Connected":
+        """One connect call (mv_connect_blocks): accept_blocks, then every NEW block joins the
+        suspended-block store and the store is swept. No blocks: a sweep alone. cap_connected None:
+        room for every suspended block. connected_out: the (cap, 8) uint64 array the call writes into."""
+        buf, offs, lens = _pack(list(blocks))
+        n = offs.shape[0]
+        grp = None if groups is None else np.ascontiguousarray(np.asarray(groups, dtype=np.uint64))
+        if grp is not None and grp.shape != (n,):
+            raise ValueError("groups: one word per block")
+        if cap_missing is None:
+            cap_missing = int(lens.sum()) // 56 + 1
+        if cap_connected is None:
+            # the suspended blocks as the host-buffer calls left them (an upper bound: no device
+            # round trip to size a buffer); after a device-buffer call the library is asked
+            known = getattr(self, "_suspended", None)
+            cap_connected = n + (self.pending_stats().suspended if known is None else known)
+        miss = np.zeros((max(cap_missing, 1), 6), dtype=np.uint64)
+        rows = connected_out if connected_out is not None else np.zeros((max(cap_connected, 1), 8), dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        state = np.zeros(max(n, 1), dtype=np.uint8)
+        nm, nc = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.lib.mv_connect_blocks(self.ctx, _p(buf), _p(offs), _p(lens), _p(grp), n, _p(st), _p(state),
+                                               _p(miss), cap_missing, ctypes.byref(nm), _p(rows), cap_connected,
+                                               ctypes.byref(nc)), "mv_connect_blocks")
+        if getattr(self, "_suspended", None) is not None:  # every NEW block joined the store, every row left it
+            joined = int(np.isin(state[:n], (ACC_NEW, ACC_SUSPENDED)).sum())
+            self._suspended = max(self._suspended + joined - int(nc.value), 0)
+        return Connected(st[:n], state[:n], miss[:min(int(nm.value), cap_missing)], int(nm.value),
+                         rows[:min(int(nc.value), cap_connected)], int(nc.value))
+
+    def dev_connect_blocks(self, device: int, d_buf, buf_bytes: int, d_off, d_len, d_grp, d_blk_status, d_blk_state,
+                           d_missing, d_connected, stream_handle: int = 0) -> Tuple[int, int]:
+        """mv_dev_connect_blocks on torch device tensors, as dev_accept_blocks; d_connected (cap, 8)
+        int64 or None. Returns the missing and the connected totals. Raises MvError with code
+        E_INDEX_FULL when the reserved index or the reserved store (pending_reserve) has no room
+        (both are unchanged)."""
+        vp = ctypes.c_void_p
+        nm, nc = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        n = d_off.shape[0] if d_off is not None else 0
+        self._suspended = None  # the states stay on the device: connect_blocks asks pending_stats next time
+        ptr = lambda t: vp(t.data_ptr()) if t is not None else None
+        self._check(self.lib.mv_dev_connect_blocks(
+            self.ctx, device, ptr(d_buf), int(buf_bytes), ptr(d_off), ptr(d_len), ptr(d_grp), n, ptr(d_blk_status),
+            ptr(d_blk_state), ptr(d_missing), d_missing.shape[0] if d_missing is not None else 0, ctypes.byref(nm),
+            ptr(d_connected), d_connected.shape[0] if d_connected is not None else 0, ctypes.byref(nc),
+            vp(stream_handle or None)), "mv_dev_connect_blocks")
+        return int(nm.value), int(nc.value)
+
+    def pending_reserve(self, blocks: int, includes: int):
+        """Room in the suspended-block store for `blocks` blocks with `includes` includes in all."""
+        self._check(self.lib.mv_pending_reserve(self.ctx, int(blocks), int(includes)), "mv_pending_reserve")
+
+    def pending_stats(self) -> "PendingStats":
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.mv_pending_stats(self.ctx, _p(out)), "mv_pending_stats")
+        self._suspended = int(out[1])
+        return PendingStats(*(int(x) for x in out))
 
     def dev_index_insert(self, device: int, d_words, stride_words: int, n: int, state: int = REF_HAVE,
                          stream_handle: int = 0, word_offset: int = 0):
@@ -907,6 +986,24 @@ class Accepted:
 
     def __init__(self, blk_status, blk_state, missing, n_missing):
         self.blk_status, self.blk_state, self.missing, self.n_missing = blk_status, blk_state, missing, n_missing
+
+
+class Connected(Accepted):
+    """Result of Engine.connect_blocks (mv_connect_blocks): Accepted, and connected: (k, 8) uint64
+    rows -- the reference, the block's index in the call or CONNECT_EARLIER, its level -- in causal
+    order; n_connected: their total (above k when cap_connected cut the list)."""
+
+    def __init__(self, blk_status, blk_state, missing, n_missing, connected, n_connected):
+        super().__init__(blk_status, blk_state, missing, n_missing)
+        self.connected, self.n_connected = connected, n_connected
+
+
+class PendingStats:
+    """Result of Engine.pending_stats (mv_pending_stats): REF_STORED entries, suspended blocks,
+    their includes, the levels of the last connect call."""
+
+    def __init__(self, stored, suspended, includes, levels):
+        self.stored, self.suspended, self.includes, self.levels = stored, suspended, includes, levels
 
 
 class WalReplay:

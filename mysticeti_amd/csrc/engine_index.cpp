@@ -21,6 +21,14 @@ constexpr int kAheadRounds = 2, kAheadRoundsShortTags = 64;
 constexpr int kMaxRounds = 1 << 16;
 
 using Index = Device::Index;
+using Pending = Device::Index::Pending;
+
+// copy k of the suspended-block store as the kernels see it
+mvk::PendStore pend_view(const Pending& pd, int k) {
+  char* b = pd.blk[k].as<char>();
+  return mvk::PendStore{(uint64_t*)b, (uint64_t*)(b + 8 * pd.cap_b), (uint64_t*)(b + 16 * pd.cap_b),
+                        (uint32_t*)(b + 24 * pd.cap_b), pd.inc[k].as<uint64_t>()};
+}
 
 // slots (a power of two) so that `entries` entries load the table to 1/2 at most; 0: too many
 uint64_t slots_for(uint64_t entries) {
@@ -82,6 +90,13 @@ mv_status index_resize(mv_ctx* ctx, Device& dev, uint64_t slots, hipStream_t s) 
   if (old_slots) {
     const mvk::IndexTable nt{fresh.as<unsigned long long>(), slots - 1, ctx->index_secret[0], ctx->index_secret[1], bits};
     HIPCHK(ctx, mvk::launch_index_rebuild(ix.tab.as<uint64_t>(), old_slots, nt, ix.ctl.as<uint64_t>(), s));
+    // the suspended-block store holds slots of the old table
+    const Pending& pd = ix.pend;
+    if (pd.nb) {
+      const mvk::PendStore p = pend_view(pd, pd.cur);
+      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, p.slot, pd.nb, ix.ctl.as<uint64_t>(), s));
+      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, p.inc, pd.ni, ix.ctl.as<uint64_t>(), s));
+    }
   }
   HIPCHK(ctx, hipStreamSynchronize(s));  // the old table is read until here; `fresh` frees it below
   std::swap(ix.tab, fresh);
@@ -136,11 +151,53 @@ mv_status insert_rounds(mv_ctx* ctx, Device& dev, const mvk::IndexKeys& ks, uint
 
 bool state_ok(uint32_t state) { return state == MV_REF_WANTED || state == MV_REF_HAVE; }
 
+// Room in the suspended-block store for more_b blocks and more_i includes on top of those there.
+// Growing keeps the records of the copy in force. Synchronises s when it grows.
+mv_status pending_room(mv_ctx* ctx, Device& dev, uint64_t more_b, uint64_t more_i, bool can_grow, hipStream_t s) {
+  Pending& pd = dev.index.pend;
+  const uint64_t need_b = pd.nb + more_b, need_i = pd.ni + more_i;
+  if (need_b <= pd.cap_b && need_i <= pd.cap_i) return MV_OK;
+  if (!can_grow)
+    return set_err(ctx, MV_E_INDEX_FULL,
+                   "suspended-block store: " + std::to_string(pd.nb) + " blocks + " + std::to_string(more_b) + " and " +
+                       std::to_string(pd.ni) + " includes + " + std::to_string(more_i) + " that the call may add > " +
+                       std::to_string(pd.cap_b) + " and " + std::to_string(pd.cap_i) + " reserved (mv_pending_reserve)");
+  if (need_b > mvk::IX_MAX_ITEMS || need_i > (1ull << 40)) return set_err(ctx, MV_E_INVALID_ARG, "too many suspended blocks");
+  Pending fresh;
+  fresh.cap_b = need_b > pd.cap_b ? std::max<uint64_t>(need_b, 2 * pd.cap_b) : pd.cap_b;
+  fresh.cap_i = need_i > pd.cap_i ? std::max<uint64_t>(need_i, 2 * pd.cap_i) : pd.cap_i;
+  for (int k = 0; k < 2; k++)
+    if (fresh.blk[k].ensure(28 * (size_t)fresh.cap_b) != hipSuccess || fresh.inc[k].ensure(8 * (size_t)fresh.cap_i) != hipSuccess) {
+      (void)hipGetLastError();
+      return set_err(ctx, MV_E_ALLOC, "no device memory for the suspended-block store");
+    }
+  if (pd.nb) {
+    const mvk::PendStore from = pend_view(pd, pd.cur), to = pend_view(fresh, 0);
+    HIPCHK(ctx, hipMemcpyAsync(to.slot, from.slot, 8 * (size_t)pd.nb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(to.ibase, from.ibase, 8 * (size_t)pd.nb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(to.blk, from.blk, 8 * (size_t)pd.nb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(to.kc, from.kc, 4 * (size_t)pd.nb, hipMemcpyDeviceToDevice, s));
+    if (pd.ni) HIPCHK(ctx, hipMemcpyAsync(to.inc, from.inc, 8 * (size_t)pd.ni, hipMemcpyDeviceToDevice, s));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(s));  // the old copies are read until here; `fresh` frees them below
+  for (int k = 0; k < 2; k++) {
+    std::swap(pd.blk[k], fresh.blk[k]);
+    std::swap(pd.inc[k], fresh.inc[k]);
+  }
+  pd.cur = 0;
+  pd.cap_b = fresh.cap_b, pd.cap_i = fresh.cap_i;
+  return MV_OK;
+}
+
 // Where accept_run leaves its results (device memory of dev.index)
 struct AcceptOut {
   uint64_t n_missing = 0;
   const uint8_t *status = nullptr, *state = nullptr;
   const uint64_t* missing = nullptr;
+  // for the connect call: the call's arrays, the candidates (their slots are in pend.cand_slot) and
+  // their includes (whose insert's records are in index.item)
+  mvk::AcceptArrays a{};
+  uint64_t ncand = 0, ninc = 0;
 };
 
 // One accept call on stream s (include/mysti_verify.h, mv_accept_blocks). Synchronises s: the
@@ -149,14 +206,14 @@ struct AcceptOut {
 // total ends the call.
 mv_status accept_run(mv_ctx* ctx, Device& dev, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_off,
                      const uint64_t* d_len, const uint64_t* d_grp, uint32_t n32, uint64_t cap_missing, bool can_grow,
-                     hipStream_t s, AcceptOut& out) {
+                     hipStream_t s, AcceptOut& out, bool connect = false) {
   Index& ix = dev.index;
   out = AcceptOut();
   const size_t n = n32;
   mv_status st = index_ctl(ctx, dev, s);
   if (st != MV_OK) return st;
   uint64_t* ctl = ix.ctl.as<uint64_t>();
-  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_NVER, 0, 8 * (mvk::IX_CTL_WORDS - mvk::IX_CTL_NVER), s));
+  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_NVER, 0, 8 * (mvk::IX_CTL_STORED - mvk::IX_CTL_NVER), s));
   // per block: known | status | state | rank | gidx | gflag | kc | cand_blk | cand_src | inc_base
   const size_t a8 = ix_al(n), a32 = ix_al(4 * n), a64 = ix_al(8 * n), nwg = mvk::index_groups(n), w64 = ix_al(8 * nwg);
   HIPCHK(ctx, ix.acc.ensure(3 * a8 + 5 * a32 + 2 * a64));
@@ -200,15 +257,27 @@ mv_status accept_run(mv_ctx* ctx, Device& dev, const uint8_t* d_buf, uint64_t bu
   if (ninc > mvk::IX_MAX_ITEMS) return set_err(ctx, MV_E_INVALID_ARG, "more than 2^32 includes in one accept call");
   out.status = a.status;
   out.state = a.state;
+  out.a = a;
   if (ncand == 0) return MV_OK;
-  // room for what the call may add, decided before the first insert (the index is unchanged until here)
+  // room for what the call may add, decided before the first insert (the index is unchanged until
+  // here; a connect call that cannot grow asks the store first, which leaves both as they are)
+  if (connect) {
+    st = pending_room(ctx, dev, ncand, ninc, can_grow, s);
+    if (st != MV_OK) return st;
+  }
   st = index_room_for_more(ctx, dev, ncand + ninc, can_grow, s);
   if (st != MV_OK) return st;
+  out.ncand = ncand;
   // 4. own references of the candidates: NEW / DUP, HAVE
   st = insert_rounds(ctx, dev, mvk::IndexKeys{d_buf, a.cand_src, 0, 1}, ncand, MV_REF_HAVE, s);
   if (st != MV_OK) return st;
   HIPCHK(ctx, mvk::launch_accept_own_states(a, ix.item.as<uint64_t>(), ncand, s));
+  if (connect) {
+    HIPCHK(ctx, ix.pend.cand_slot.ensure(8 * (size_t)ncand));
+    HIPCHK(ctx, mvk::launch_pend_own_slots(ix.item.as<uint64_t>(), ncand, ix.pend.cand_slot.as<uint64_t>(), s));
+  }
   if (ninc == 0) return MV_OK;
+  out.ninc = ninc;
   // 5. includes of the NEW blocks: WANTED, the missing list
   HIPCHK(ctx, ix.keys.ensure(8 * (size_t)ninc));
   uint64_t* inc_src = ix.keys.as<uint64_t>();
@@ -235,6 +304,143 @@ mv_status index_dev(mv_ctx* ctx, Device*& dev) {
   reap_idle(ctx, *dev);
   return order_behind_ahead(ctx, *dev, dev->stream);
 }
+
+// The host-buffer calls' way in: the blocks' bytes and the off | len | grp table go to the device,
+// then accept_run.
+mv_status stage_blocks(mv_ctx* ctx, Device& dev, const uint8_t* buf, const uint64_t* off, const uint64_t* len,
+                       const uint64_t* grp, uint32_t n, uint64_t cap_missing, hipStream_t s, AcceptOut& ao, bool connect) {
+  Index& ix = dev.index;
+  // the bytes: pinned, in order and disjoint blocks as one DMA of the caller's memory in place;
+  // else packed block by block (8-byte aligned, which also separates overlapping blocks)
+  uint64_t bytes = 0, span = 0;
+  const uint64_t first = off[0];
+  bool direct = host_pinned(buf + first);
+  for (uint32_t k = 0; k < n; k++) {
+    bytes += (len[k] + 7) & ~7ull;
+    if (direct && (off[k] < first || off[k] - first < span)) direct = false;
+    if (direct) span = off[k] - first + len[k];
+  }
+  direct = direct && span && span <= 2 * bytes + 4096 && pinned_range_holds(buf + first, span);
+  const uint64_t buf_bytes = direct ? span : bytes;
+  const size_t nn = n;
+  std::vector<uint64_t> tab((grp ? 3 : 2) * nn);  // device offsets | lengths | groups
+  HIPCHK(ctx, ix.in.ensure(buf_bytes + 32));
+  uint8_t* d_buf = ix.in.as<uint8_t>();
+  if (direct) {
+    for (size_t k = 0; k < nn; k++) tab[k] = off[k] - first;
+    HIPCHK(ctx, hipMemcpyAsync(d_buf, buf + first, span, hipMemcpyHostToDevice, s));
+  } else {
+    HIPCHK(ctx, dev.hc.h_in.ensure(bytes + 32));
+    uint8_t* h = dev.hc.h_in.as<uint8_t>();
+    uint64_t p = 0;
+    for (size_t k = 0; k < nn; k++) {
+      const uint64_t l = len[k], pl = (l + 7) & ~7ull;
+      if (l) memcpy(h + p, buf + off[k], l);
+      memset(h + p + l, 0, pl - l);
+      tab[k] = p;
+      p += pl;
+    }
+    if (bytes) HIPCHK(ctx, hipMemcpyAsync(d_buf, h, bytes, hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(ctx, hipMemsetAsync(d_buf + buf_bytes, 0, 32, s));  // the readable bytes past the last block
+  memcpy(tab.data() + nn, len, 8 * nn);
+  if (grp) memcpy(tab.data() + 2 * nn, grp, 8 * nn);
+  HIPCHK(ctx, ix.tab_in.ensure(8 * tab.size()));
+  HIPCHK(ctx, hipMemcpyAsync(ix.tab_in.p, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, s));
+  const uint64_t* d_tab = ix.tab_in.as<uint64_t>();
+  return accept_run(ctx, dev, d_buf, buf_bytes, d_tab, d_tab + nn, grp ? d_tab + 2 * nn : nullptr, n, cap_missing,
+                  /*can_grow=*/true, s, ao, connect);
+}
+
+// Step 6 of a connect call on stream s, after accept_run (or alone: n = 0): the NEW blocks join the
+// store, the sweep, the compaction. Rows go to d_rows (cap rows; the caller's device memory, or
+// pend.rows). Synchronises s: the appended counts, the level counts of every few levels enqueued
+// together, and what the compaction kept are read back.
+mv_status connect_sweep(mv_ctx* ctx, Device& dev, const AcceptOut& ao, uint64_t* d_rows, uint64_t cap, hipStream_t s,
+                        uint64_t* n_connected) {
+  Index& ix = dev.index;
+  Pending& pd = ix.pend;
+  *n_connected = 0;
+  pd.levels = 0;
+  mv_status st = index_ctl(ctx, dev, s);
+  if (st != MV_OK) return st;
+  uint64_t* ctl = ix.ctl.as<uint64_t>();
+  const uint64_t* h = nullptr;
+  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_PB_NB, 0, 8 * (mvk::IX_CTL_WORDS - mvk::IX_CTL_PB_NB), s));
+  if (ao.ncand) {  // (accept_run made room for ncand blocks and ninc includes)
+    const size_t w64 = 8 * mvk::index_groups(ao.ncand);
+    HIPCHK(ctx, ix.wg.ensure(4 * w64));
+    HIPCHK(ctx, pd.cand_dst.ensure(8 * (size_t)ao.ncand));
+    HIPCHK(ctx, mvk::launch_pend_append(ao.a, ao.ncand, ao.ninc, ix.item.as<uint64_t>(), pd.cand_slot.as<uint64_t>(),
+                                        pd.cand_dst.as<uint64_t>(), pend_view(pd, pd.cur), pd.nb, pd.ni,
+                                        ix.wg.as<uint64_t>(), ctl, s));
+    st = read_ctl(ctx, dev, s, &h);
+    if (st != MV_OK) return st;
+    pd.nb += std::min<uint64_t>(h[mvk::IX_CTL_PB_NB], ao.ncand);
+    pd.ni += std::min<uint64_t>(h[mvk::IX_CTL_PB_NI], ao.ninc);
+  }
+  const uint64_t nb = pd.nb;
+  if (nb == 0) return MV_OK;
+  const mvk::IndexTable t = table_of(ctx, ix);
+  const mvk::PendStore p = pend_view(pd, pd.cur), q = pend_view(pd, pd.cur ^ 1);
+  HIPCHK(ctx, ix.wg.ensure(4 * 8 * mvk::index_groups(nb)));
+  HIPCHK(ctx, pd.lvl.ensure(4 * (size_t)nb));
+  HIPCHK(ctx, pd.hit.ensure((size_t)nb));
+  HIPCHK(ctx, pd.newbase.ensure(8 * (size_t)nb));
+  HIPCHK(ctx, hipMemsetAsync(pd.lvl.p, 0, 4 * (size_t)nb, s));
+  // the sweep: levels are enqueued 2, 4, 8, then 16 at a time and their counts read together; a
+  // level past the fixed point lists nothing. At most nb levels connect something.
+  uint64_t level = 0;
+  for (int ahead = 2;; ahead = std::min(2 * ahead, mvk::IX_CTL_LEVELS)) {
+    HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_LV0, 0, 8 * mvk::IX_CTL_LEVELS, s));
+    const int m = (int)std::min<uint64_t>(ahead, nb + 1 - level);
+    for (int k = 0; k < m; k++)
+      HIPCHK(ctx, mvk::launch_pend_level(t, p, nb, pd.lvl.as<uint32_t>(), pd.hit.as<uint8_t>(), level + k,
+                                         ix.wg.as<uint64_t>(), d_rows, cap, ctl, mvk::IX_CTL_LV0 + k, s));
+    st = read_ctl(ctx, dev, s, &h);
+    if (st != MV_OK) return st;
+    int k = 0;
+    while (k < m && h[mvk::IX_CTL_LV0 + k]) k++;
+    level += k;
+    if (k < m) break;
+    if (level > nb) return set_err(ctx, MV_E_HIP, "connect: the sweep did not reach its fixed point");
+  }
+  pd.levels = level;
+  *n_connected = h[mvk::IX_CTL_PB_ROWS];
+  // what stays is blocks_pending
+  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_PB_NB, 0, 16, s));
+  HIPCHK(ctx, mvk::launch_pend_compact(t, p, q, nb, pd.newbase.as<uint64_t>(), ao.a.state, ao.a.n, ix.wg.as<uint64_t>(), ctl, s));
+  st = read_ctl(ctx, dev, s, &h);
+  if (st != MV_OK) return st;
+  pd.nb = std::min<uint64_t>(h[mvk::IX_CTL_PB_NB], nb);
+  pd.ni = std::min<uint64_t>(h[mvk::IX_CTL_PB_NI], pd.ni);
+  pd.cur ^= 1;
+  return MV_OK;
+}
+
+// mv_index_insert / mv_index_insert_stored
+mv_status index_insert_host(mv_ctx* ctx, const uint64_t* refs, uint64_t n, uint32_t state, uint8_t* prior) {
+  if (n == 0) return MV_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  Index& ix = dev->index;
+  hipStream_t s = dev->stream;
+  st = index_room_for_more(ctx, *dev, n, /*can_grow=*/true, s);
+  if (st != MV_OK) return st;
+  HIPCHK(ctx, ix.keys.ensure(48 * (size_t)n));
+  HIPCHK(ctx, hipMemcpyAsync(ix.keys.p, refs, 48 * (size_t)n, hipMemcpyHostToDevice, s));
+  st = insert_rounds(ctx, *dev, mvk::IndexKeys{ix.keys.as<uint8_t>(), nullptr, 48, 0}, n, state, s);
+  if (st != MV_OK) return st;
+  if (prior) {
+    HIPCHK(ctx, ix.out.ensure((size_t)n));
+    HIPCHK(ctx, mvk::launch_index_prior(ix.item.as<uint64_t>(), n, ix.out.as<uint8_t>(), s));
+    HIPCHK(ctx, hipMemcpyAsync(prior, ix.out.p, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+  }
+  return MV_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -259,6 +465,7 @@ mv_status mv_index_clear(mv_ctx* ctx) {
   mv_status st = index_dev(ctx, dev);
   if (st != MV_OK) return st;
   Index& ix = dev->index;
+  ix.pend.nb = ix.pend.ni = ix.pend.levels = 0;  // the store's records are slots of the table
   if (!ix.slots) return MV_OK;
   HIPCHK(ctx, hipMemsetAsync(ix.tab.p, 0, kSlotBytes * ix.slots, dev->stream));
   HIPCHK(ctx, hipMemsetAsync(ix.ctl.p, 0, 8 * mvk::IX_CTL_WORDS, dev->stream));
@@ -291,26 +498,12 @@ mv_status mv_index_stats(mv_ctx* ctx, uint64_t* out) {
 mv_status mv_index_insert(mv_ctx* ctx, const uint64_t* refs, uint64_t n, uint32_t state, uint8_t* prior) {
   if (!ctx || (n && !refs) || !state_ok(state) || n > mvk::IX_MAX_ITEMS)
     return set_err(ctx, MV_E_INVALID_ARG, "bad index_insert args");
-  if (n == 0) return MV_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  Device* dev;
-  mv_status st = index_dev(ctx, dev);
-  if (st != MV_OK) return st;
-  Index& ix = dev->index;
-  hipStream_t s = dev->stream;
-  st = index_room_for_more(ctx, *dev, n, /*can_grow=*/true, s);
-  if (st != MV_OK) return st;
-  HIPCHK(ctx, ix.keys.ensure(48 * (size_t)n));
-  HIPCHK(ctx, hipMemcpyAsync(ix.keys.p, refs, 48 * (size_t)n, hipMemcpyHostToDevice, s));
-  st = insert_rounds(ctx, *dev, mvk::IndexKeys{ix.keys.as<uint8_t>(), nullptr, 48, 0}, n, state, s);
-  if (st != MV_OK) return st;
-  if (prior) {
-    HIPCHK(ctx, ix.out.ensure((size_t)n));
-    HIPCHK(ctx, mvk::launch_index_prior(ix.item.as<uint64_t>(), n, ix.out.as<uint8_t>(), s));
-    HIPCHK(ctx, hipMemcpyAsync(prior, ix.out.p, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-  }
-  return MV_OK;
+  return index_insert_host(ctx, refs, n, state, prior);
+}
+
+mv_status mv_index_insert_stored(mv_ctx* ctx, const uint64_t* refs, uint64_t n, uint8_t* prior) {
+  if (!ctx || (n && !refs) || n > mvk::IX_MAX_ITEMS) return set_err(ctx, MV_E_INVALID_ARG, "bad index_insert_stored args");
+  return index_insert_host(ctx, refs, n, MV_REF_STORED, prior);
 }
 
 mv_status mv_index_lookup(mv_ctx* ctx, const uint64_t* refs, uint64_t n, uint8_t* state) {
@@ -376,49 +569,10 @@ mv_status mv_accept_blocks(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off,
   Device* dev;
   mv_status st = index_dev(ctx, dev);
   if (st != MV_OK) return st;
-  Index& ix = dev->index;
   hipStream_t s = dev->stream;
-  // the bytes: pinned, in order and disjoint blocks as one DMA of the caller's memory in place;
-  // else packed block by block (8-byte aligned, which also separates overlapping blocks)
-  uint64_t bytes = 0, span = 0;
-  const uint64_t first = off[0];
-  bool direct = host_pinned(buf + first);
-  for (uint32_t k = 0; k < n; k++) {
-    bytes += (len[k] + 7) & ~7ull;
-    if (direct && (off[k] < first || off[k] - first < span)) direct = false;
-    if (direct) span = off[k] - first + len[k];
-  }
-  direct = direct && span && span <= 2 * bytes + 4096 && pinned_range_holds(buf + first, span);
-  const uint64_t buf_bytes = direct ? span : bytes;
   const size_t nn = n;
-  std::vector<uint64_t> tab((grp ? 3 : 2) * nn);  // device offsets | lengths | groups
-  HIPCHK(ctx, ix.in.ensure(buf_bytes + 32));
-  uint8_t* d_buf = ix.in.as<uint8_t>();
-  if (direct) {
-    for (size_t k = 0; k < nn; k++) tab[k] = off[k] - first;
-    HIPCHK(ctx, hipMemcpyAsync(d_buf, buf + first, span, hipMemcpyHostToDevice, s));
-  } else {
-    HIPCHK(ctx, dev->hc.h_in.ensure(bytes + 32));
-    uint8_t* h = dev->hc.h_in.as<uint8_t>();
-    uint64_t p = 0;
-    for (size_t k = 0; k < nn; k++) {
-      const uint64_t l = len[k], pl = (l + 7) & ~7ull;
-      if (l) memcpy(h + p, buf + off[k], l);
-      memset(h + p + l, 0, pl - l);
-      tab[k] = p;
-      p += pl;
-    }
-    if (bytes) HIPCHK(ctx, hipMemcpyAsync(d_buf, h, bytes, hipMemcpyHostToDevice, s));
-  }
-  HIPCHK(ctx, hipMemsetAsync(d_buf + buf_bytes, 0, 32, s));  // the readable bytes past the last block
-  memcpy(tab.data() + nn, len, 8 * nn);
-  if (grp) memcpy(tab.data() + 2 * nn, grp, 8 * nn);
-  HIPCHK(ctx, ix.tab_in.ensure(8 * tab.size()));
-  HIPCHK(ctx, hipMemcpyAsync(ix.tab_in.p, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, s));
-  const uint64_t* d_tab = ix.tab_in.as<uint64_t>();
   AcceptOut ao;
-  st = accept_run(ctx, *dev, d_buf, buf_bytes, d_tab, d_tab + nn, grp ? d_tab + 2 * nn : nullptr, n, cap_missing,
-                  /*can_grow=*/true, s, ao);
+  st = stage_blocks(ctx, *dev, buf, off, len, grp, n, cap_missing, s, ao, /*connect=*/false);
   if (st != MV_OK) {
     (void)hipStreamSynchronize(s);  // (the copies above may still be in flight)
     return st;
@@ -468,7 +622,8 @@ mv_status mv_dev_accept_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, ui
 
 mv_status mv_dev_index_insert(mv_ctx* ctx, int device, const uint64_t* d_words, uint64_t stride_words, uint64_t n,
                               uint32_t state, void* stream) {
-  if (!ctx || (n && !d_words) || stride_words < mv::br::KEY_WORDS || !state_ok(state) || n > mvk::IX_MAX_ITEMS ||
+  if (!ctx || (n && !d_words) || stride_words < mv::br::KEY_WORDS || !(state_ok(state) || state == MV_REF_STORED) ||
+      n > mvk::IX_MAX_ITEMS ||
       (((uintptr_t)d_words) & 7))
     return set_err(ctx, MV_E_INVALID_ARG, "bad index_insert args");
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -499,6 +654,118 @@ mv_status mv_dev_index_insert(mv_ctx* ctx, int device, const uint64_t* d_words, 
   ix.ahead_set = true;
   ix.used += n;
   ix.used_exact = false;
+  return MV_OK;
+}
+
+
+mv_status mv_pending_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t includes) {
+  if (!ctx) return MV_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  const Pending& pd = dev->index.pend;
+  return pending_room(ctx, *dev, blocks > pd.nb ? blocks - pd.nb : 0, includes > pd.ni ? includes - pd.ni : 0,
+                      /*can_grow=*/true, dev->stream);
+}
+
+mv_status mv_pending_stats(mv_ctx* ctx, uint64_t* out) {
+  if (!ctx || !out) return set_err(ctx, MV_E_INVALID_ARG, "bad pending_stats args");
+  memset(out, 0, 4 * sizeof(uint64_t));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  Index& ix = dev->index;
+  out[1] = ix.pend.nb, out[2] = ix.pend.ni, out[3] = ix.pend.levels;
+  if (!ix.ctl.p) return MV_OK;
+  const uint64_t* w = nullptr;
+  st = read_ctl(ctx, *dev, dev->stream, &w);
+  out[0] = w ? w[mvk::IX_CTL_STORED] : 0;
+  return st;
+}
+
+mv_status mv_connect_blocks(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off, const uint64_t* len, const uint64_t* grp,
+                            uint32_t n, uint8_t* blk_status, uint8_t* blk_state, uint64_t* missing, uint64_t cap_missing,
+                            uint64_t* n_missing, uint64_t* connected, uint64_t cap_connected, uint64_t* n_connected) {
+  if (!ctx || !n_missing || !n_connected || (n && (!buf || !off || !len || !blk_status || !blk_state)) ||
+      (cap_missing && !missing) || (cap_connected && !connected))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad connect args");
+  *n_missing = *n_connected = 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!committee_ready(ctx)) return set_err(ctx, MV_E_NO_COMMITTEE, "mv_set_committee first");
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  Index& ix = dev->index;
+  hipStream_t s = dev->stream;
+  AcceptOut ao;
+  const size_t nn = n;
+  if (n) {
+    st = stage_blocks(ctx, *dev, buf, off, len, grp, n, cap_missing, s, ao, /*connect=*/true);
+    if (st != MV_OK) {
+      (void)hipStreamSynchronize(s);  // (the copies may still be in flight)
+      return st;
+    }
+  }
+  // the rows: at most the records the store holds once this call's blocks joined it
+  const uint64_t capd = std::min<uint64_t>(cap_connected, ix.pend.nb + ao.ncand);
+  HIPCHK(ctx, ix.pend.rows.ensure(64 * (size_t)capd + 8));
+  uint64_t total = 0;
+  st = connect_sweep(ctx, *dev, ao, ix.pend.rows.as<uint64_t>(), capd, s, &total);
+  if (st != MV_OK) {
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  if (n) {
+    HIPCHK(ctx, hipMemcpyAsync(blk_status, ao.status, nn, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(blk_state, ao.state, nn, hipMemcpyDeviceToHost, s));
+  }
+  const uint64_t wr = std::min(ao.n_missing, cap_missing), wc = std::min(total, capd);
+  if (wr) HIPCHK(ctx, hipMemcpyAsync(missing, ao.missing, 48 * (size_t)wr, hipMemcpyDeviceToHost, s));
+  if (wc) HIPCHK(ctx, hipMemcpyAsync(connected, ix.pend.rows.p, 64 * (size_t)wc, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  *n_missing = ao.n_missing;
+  *n_connected = total;
+  return MV_OK;
+}
+
+mv_status mv_dev_connect_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_off,
+                                const uint64_t* d_len, const uint64_t* d_grp, uint32_t n, uint8_t* d_blk_status,
+                                uint8_t* d_blk_state, uint64_t* d_missing, uint64_t cap_missing, uint64_t* n_missing,
+                                uint64_t* d_connected, uint64_t cap_connected, uint64_t* n_connected, void* stream) {
+  if (!ctx || !n_missing || !n_connected || (n && (!d_buf || !d_off || !d_len || !d_blk_status || !d_blk_state)) ||
+      (cap_missing && !d_missing) || (cap_connected && !d_connected))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad connect args");
+  if (((uintptr_t)d_buf) & 7) return set_err(ctx, MV_E_INVALID_ARG, "d_buf must be 8-byte aligned");
+  *n_missing = *n_connected = 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!committee_ready(ctx)) return set_err(ctx, MV_E_NO_COMMITTEE, "mv_set_committee first");
+  Device* dev = find_dev(ctx, device);
+  if (!dev || dev != &ctx->devs[0]) return set_err(ctx, MV_E_NO_DEVICE, "the index lives on the context's first device");
+  HIPCHK(ctx, hipSetDevice(dev->id));
+  reap_idle(ctx, *dev);
+  hipStream_t s = stream ? (hipStream_t)stream : dev->stream;
+  mv_status st = order_behind_ahead(ctx, *dev, s);
+  if (st != MV_OK) return st;
+  AcceptOut ao;
+  if (n) st = accept_run(ctx, *dev, d_buf, buf_bytes, d_off, d_len, d_grp, n, cap_missing, /*can_grow=*/false, s, ao,
+                         /*connect=*/true);
+  uint64_t total = 0;
+  if (st == MV_OK) st = connect_sweep(ctx, *dev, ao, d_connected, cap_connected, s, &total);
+  if (st != MV_OK) {
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  if (n) {
+    HIPCHK(ctx, hipMemcpyAsync(d_blk_status, ao.status, (size_t)n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_blk_state, ao.state, (size_t)n, hipMemcpyDeviceToDevice, s));
+  }
+  const uint64_t wr = std::min(ao.n_missing, cap_missing);
+  if (wr) HIPCHK(ctx, hipMemcpyAsync(d_missing, ao.missing, 48 * (size_t)wr, hipMemcpyDeviceToDevice, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  *n_missing = ao.n_missing;
+  *n_connected = total;
   return MV_OK;
 }
 

@@ -181,6 +181,15 @@ struct Device {
     bool ahead_set = false;
     uint64_t rebuilds = 0;
     uint32_t tag_bits = 64;      // of the table in force
+    // mv_connect_blocks: the suspended-block store (mvk::PendStore), two copies -- blk[k] holds
+    // slot | ibase | blk | kc for cap_b records, inc[k] cap_i include slots -- of which `cur` is in
+    // force; a call compacts into the other and swaps
+    struct Pending {
+      DevBuf blk[2], inc[2];
+      int cur = 0;
+      uint64_t nb = 0, ni = 0, cap_b = 0, cap_i = 0, levels = 0;
+      DevBuf cand_slot, cand_dst, lvl, hit, newbase, rows;  // per candidate | per record scratch, the rows
+    } pend;
   } index;
 
   // the resident online service (k_online) of this device, made on first use

@@ -442,10 +442,14 @@ constexpr uint64_t IX_NO_SRC = ~0ull;
 constexpr uint64_t IX_MAX_ITEMS = 0xfffffffeull;  // items of one insert (the owner word holds ~item)
 // control words (device, u64): the HAVE and WANTED entries, the longest probe since the last clear,
 // items left for another round, probes that ran through the table (sticky: MV_E_HIP), then the
-// totals of the accept call's scans and of the WANTED list
+// totals of the accept call's scans and of the WANTED list (zeroed by every accept call), the STORED
+// entries (HAVE counts them too), and the connect call's words: blocks and includes appended to or
+// kept in the suspended-block store, the rows listed so far, and the rows of each level of the
+// levels enqueued together
 constexpr int IX_CTL_HAVE = 0, IX_CTL_WANTED = 1, IX_CTL_MAXPROBE = 2, IX_CTL_RETRY = 3, IX_CTL_ERR = 4,
               IX_CTL_NVER = 5, IX_CTL_NHEADS = 6, IX_CTL_NCAND = 7, IX_CTL_NINC = 8, IX_CTL_NMISS = 9,
-              IX_CTL_NWANTED = 10, IX_CTL_WORDS = 16;
+              IX_CTL_NWANTED = 10, IX_CTL_STORED = 11, IX_CTL_PB_NB = 12, IX_CTL_PB_NI = 13, IX_CTL_PB_ROWS = 14,
+              IX_CTL_LV0 = 16, IX_CTL_LEVELS = 16, IX_CTL_WORDS = IX_CTL_LV0 + IX_CTL_LEVELS;
 uint64_t index_groups(uint64_t n);  // workgroups of the per-item kernels: wgcount / wgbase hold one word each
 hipError_t launch_index_scan(const uint64_t* wgcount, uint64_t nwg, uint64_t* wgbase, uint64_t* total, hipStream_t s);
 // one insert round (k_ix_claim, k_ix_fill, k_ix_settle) of n items towards `state`; item: n words
@@ -494,4 +498,36 @@ hipError_t launch_accept_own_states(const AcceptArrays& a, const uint64_t* item,
 hipError_t launch_accept_inc_src(const AcceptArrays& a, uint64_t ncand, uint64_t ninc, uint64_t* inc_src, hipStream_t s);
 hipError_t launch_accept_missing(const IndexTable& t, const uint64_t* item, uint64_t ninc, uint64_t* wgcount,
                                  uint64_t* wgbase, uint64_t* ctl, uint64_t* out, uint64_t cap, hipStream_t s);
+
+// The suspended-block store (mv_connect_blocks; layout and sweep: index.hip): one record per block
+// whose includes are not all MV_REF_STORED, in arrival order. The engine keeps two copies and
+// compacts from one into the other. References are held as slots of the table: a rebuild
+// re-resolves them (launch_pend_reresolve).
+struct PendStore {
+  uint64_t* slot;   // per block: the slot of its own reference
+  uint64_t* ibase;  // the number of its first include in inc
+  uint64_t* blk;    // its index in the call that is running, IX_NO_SRC when an earlier call suspended it
+  uint32_t* kc;     // its include count
+  uint64_t* inc;    // per include: its slot
+};
+// cand_slot[r] = the slot of candidate r's own reference (its insert's records, before the includes' overwrite them)
+hipError_t launch_pend_own_slots(const uint64_t* item, uint64_t ncand, uint64_t* cand_slot, hipStream_t s);
+// The NEW blocks of an accept call join the store behind its nb0 blocks and ni0 includes, in block
+// order; item: the records of the includes' insert. ctl[IX_CTL_PB_NB], ctl[IX_CTL_PB_NI] = how many.
+hipError_t launch_pend_append(const AcceptArrays& a, uint64_t ncand, uint64_t ninc, const uint64_t* item,
+                              const uint64_t* cand_slot, uint64_t* cand_dst, const PendStore& p, uint64_t nb0, uint64_t ni0,
+                              uint64_t* wg /* 4 x index_groups(ncand) */, uint64_t* ctl, hipStream_t s);
+// One level of the sweep over the nb records: check (a wave per record), count, scan, list + raise.
+// lvl[b]: 0, or 1 + the level that connected b. Rows go to out (cap rows of 8 words) from row
+// ctl[IX_CTL_PB_ROWS] on; ctl[lv_word] = the rows of this level.
+hipError_t launch_pend_level(const IndexTable& t, const PendStore& p, uint64_t nb, uint32_t* lvl, uint8_t* hit,
+                             uint64_t level, uint64_t* wg /* 2 x index_groups(nb) */, uint64_t* out, uint64_t cap,
+                             uint64_t* ctl, int lv_word, hipStream_t s);
+// Stable compaction of p's records that are not STORED into q; those of the running call become
+// MV_ACC_SUSPENDED in state (n_state entries, may be null). ctl[IX_CTL_PB_NB], ctl[IX_CTL_PB_NI] = what q holds.
+hipError_t launch_pend_compact(const IndexTable& t, const PendStore& p, const PendStore& q, uint64_t nb, uint64_t* newbase,
+                               uint8_t* state, uint64_t n_state, uint64_t* wg /* 4 x index_groups(nb) */, uint64_t* ctl, hipStream_t s);
+// after launch_index_rebuild: n slot numbers of the old table become those of the same keys in t
+hipError_t launch_pend_reresolve(const uint64_t* old_slots, const IndexTable& t, uint64_t* slotidx, uint64_t n,
+                                 uint64_t* ctl, hipStream_t s);
 }  // namespace mvk

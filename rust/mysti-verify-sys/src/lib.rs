@@ -28,12 +28,14 @@ pub const MV_E_INDEX_FULL: i32 = -6;
 pub const MV_REF_ABSENT: u8 = 0;
 pub const MV_REF_WANTED: u8 = 1;
 pub const MV_REF_HAVE: u8 = 2;
+pub const MV_REF_STORED: u8 = 3;
 
 pub const MV_ACC_REJECTED: u8 = 0;
 pub const MV_ACC_NEW: u8 = 1;
 pub const MV_ACC_KNOWN: u8 = 2;
 pub const MV_ACC_DUP: u8 = 3;
 pub const MV_ACC_DROPPED: u8 = 4;
+pub const MV_ACC_SUSPENDED: u8 = 5;
 
 pub const MV_SIG_OK: u8 = 0;
 pub const MV_SIG_INVALID: u8 = 1;
@@ -119,6 +121,7 @@ extern "C" {
     pub fn mv_index_clear(ctx: *mut mv_ctx) -> i32;
     pub fn mv_index_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
     pub fn mv_index_insert(ctx: *mut mv_ctx, refs: *const u64, n: u64, state: u32, prior: *mut u8) -> i32;
+    pub fn mv_index_insert_stored(ctx: *mut mv_ctx, refs: *const u64, n: u64, prior: *mut u8) -> i32;
     pub fn mv_index_lookup(ctx: *mut mv_ctx, refs: *const u64, n: u64, state: *mut u8) -> i32;
     pub fn mv_index_wanted(ctx: *mut mv_ctx, refs: *mut u64, cap: u64, n: *mut u64) -> i32;
     pub fn mv_accept_blocks(ctx: *mut mv_ctx, buf: *const u8, off: *const u64, len: *const u64,
@@ -128,6 +131,17 @@ extern "C" {
                                 d_off: *const u64, d_len: *const u64, d_grp: *const u64, n: u32,
                                 d_blk_status: *mut u8, d_blk_state: *mut u8, d_missing: *mut u64,
                                 cap_missing: u64, n_missing: *mut u64, stream: *mut c_void) -> i32;
+    pub fn mv_connect_blocks(ctx: *mut mv_ctx, buf: *const u8, off: *const u64, len: *const u64,
+                             grp: *const u64, n: u32, blk_status: *mut u8, blk_state: *mut u8,
+                             missing: *mut u64, cap_missing: u64, n_missing: *mut u64,
+                             connected: *mut u64, cap_connected: u64, n_connected: *mut u64) -> i32;
+    pub fn mv_dev_connect_blocks(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,
+                                 d_off: *const u64, d_len: *const u64, d_grp: *const u64, n: u32,
+                                 d_blk_status: *mut u8, d_blk_state: *mut u8, d_missing: *mut u64,
+                                 cap_missing: u64, n_missing: *mut u64, d_connected: *mut u64,
+                                 cap_connected: u64, n_connected: *mut u64, stream: *mut c_void) -> i32;
+    pub fn mv_pending_reserve(ctx: *mut mv_ctx, blocks: u64, includes: u64) -> i32;
+    pub fn mv_pending_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
     pub fn mv_dev_index_insert(ctx: *mut mv_ctx, device: i32, d_words: *const u64, stride_words: u64, n: u64,
                                state: u32, stream: *mut c_void) -> i32;
     pub fn mv_dev_verify_frames(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,

@@ -6,6 +6,7 @@
 //! failing status back into the exact `eyre` error `StatementBlock::verify` would have
 //! returned. The message text needs the failing values (digests, the include, the range), so
 //! for a rejected block the wrapper re-reads them host-side -- only on that failure path.
+use std::sync::atomic::{AtomicU64, Ordering};
 use std::sync::Arc;
 
 use eyre::{bail, ensure};
@@ -19,6 +20,9 @@ use crate::types::{BaseStatement, StatementBlock};
 
 pub struct GpuVerifier {
     ctx: *mut sys::mv_ctx,
+    // the blocks `connect_blocks` left suspended (an upper bound): sizes its row buffer without a
+    // device round trip. Connect calls are the core's and come one at a time.
+    suspended: AtomicU64,
 }
 // mv_* calls are thread-safe on one context; concurrent callers are merged by the engine's
 // submission queue (one device pass serves all of them)
@@ -38,7 +42,7 @@ impl GpuVerifier {
         let mut ctx = std::ptr::null_mut();
         let cfg = sys::mv_config { device_mask, ..Default::default() };
         ensure!(unsafe { sys::mv_create(&cfg, &mut ctx) } == sys::MV_OK, "no gfx950 device in mask {device_mask:#x}");
-        let me = Self { ctx };
+        let me = Self { ctx, suspended: AtomicU64::new(0) };
         let pks: Vec<u8> = committee
             .authorities()
             .flat_map(|a| committee.get_public_key(a).unwrap().0.as_bytes().to_vec())
@@ -176,6 +180,19 @@ impl GpuVerifier {
         Ok(())
     }
 
+    /// Seeds references of blocks that are in the store as MV_REF_STORED: what a caller of
+    /// `connect_blocks` uses in place of `index_insert_have` for the genesis references and a
+    /// replay's rows, and for its own proposed block (then `connect_blocks` with no blocks sweeps).
+    /// A context seeded with MV_REF_HAVE never connects anything.
+    pub fn index_insert_stored(&self, refs: &[u64]) -> eyre::Result<()> {
+        ensure!(refs.len() % 6 == 0, "six words per reference");
+        let rc = unsafe {
+            sys::mv_index_insert_stored(self.ctx, refs.as_ptr(), (refs.len() / 6) as u64, std::ptr::null_mut())
+        };
+        ensure!(rc == sys::MV_OK, "mv_index_insert_stored: {}", self.last_error());
+        Ok(())
+    }
+
     /// BlockManager::missing_blocks (block_manager.rs:138-140) as the index holds it: the
     /// MV_REF_WANTED references, six words each, in no particular order.
     pub fn index_wanted(&self) -> eyre::Result<Vec<u64>> {
@@ -195,7 +212,7 @@ impl GpuVerifier {
     /// BlockManager::add_blocks (block_manager.rs:62-98) whose result the syncer requests from
     /// peers (net_sync.rs:388-398). `groups[i]` names the message of block i (non-decreasing).
     /// The caller hands the MV_ACC_NEW blocks to the core, which keeps the suspend / unlock
-    /// cascade (blocks_pending) and the WAL write.
+    /// cascade (blocks_pending) and the WAL write; `connect_blocks` runs the cascade too.
     pub fn accept_blocks(&self, buf: &[u8], blocks: &[(u64, u64)], groups: &[u64]) -> eyre::Result<Accepted> {
         ensure!(groups.len() == blocks.len(), "one group word per block");
         let n = blocks.len();
@@ -220,6 +237,51 @@ impl GpuVerifier {
         }
         Ok(out)
     }
+
+    /// The whole of BlockManager::add_blocks but the block bodies and the WAL write
+    /// (mv_connect_blocks): `accept_blocks`, then the suspend / unlock cascade
+    /// (block_manager.rs:102-131) over the suspended blocks the context keeps in device memory.
+    /// The rows name the blocks the core may process now, in an order in which every include comes
+    /// before its includer: the caller appends them to its WAL and hands them on in that order,
+    /// keeping the bodies of MV_ACC_SUSPENDED blocks by reference until a later call lists them.
+    /// No blocks: a sweep alone.
+    pub fn connect_blocks(&self, buf: &[u8], blocks: &[(u64, u64)], groups: &[u64]) -> eyre::Result<Connected> {
+        ensure!(groups.len() == blocks.len(), "one group word per block");
+        let n = blocks.len();
+        let off: Vec<u64> = blocks.iter().map(|b| b.0).collect();
+        let len: Vec<u64> = blocks.iter().map(|b| b.1).collect();
+        let before = self.suspended.load(Ordering::Relaxed);
+        let cap_rows = n + before as usize; // every row: this call's blocks and the suspended ones
+        let mut acc = Accepted { blk_status: vec![0; n], blk_state: vec![0; n], missing: Vec::new() };
+        let cap = 64 * n.max(1);
+        acc.missing.resize(6 * cap, 0);
+        let mut connected = vec![0u64; 8 * cap_rows.max(1)];
+        let (mut n_missing, mut n_connected) = (0u64, 0u64);
+        let rc = unsafe {
+            sys::mv_connect_blocks(self.ctx, buf.as_ptr(), off.as_ptr(), len.as_ptr(), groups.as_ptr(), n as u32,
+                                   acc.blk_status.as_mut_ptr(), acc.blk_state.as_mut_ptr(), acc.missing.as_mut_ptr(),
+                                   cap as u64, &mut n_missing, connected.as_mut_ptr(), cap_rows as u64,
+                                   &mut n_connected)
+        };
+        ensure!(rc == sys::MV_OK, "mv_connect_blocks: {}", self.last_error());
+        if n_missing as usize <= cap {
+            acc.missing.truncate(6 * n_missing as usize);
+        } else {
+            acc.missing = self.index_wanted()?;
+        }
+        connected.truncate(8 * n_connected as usize);
+        // every NEW block joined the store (parked ones say SUSPENDED), every row left it
+        let joined = acc.blk_state.iter().filter(|&&s| s == sys::MV_ACC_NEW || s == sys::MV_ACC_SUSPENDED).count() as u64;
+        self.suspended.store((before + joined).saturating_sub(n_connected), Ordering::Relaxed);
+        Ok(Connected { accepted: acc, connected })
+    }
+}
+
+/// Result of `GpuVerifier::connect_blocks` (layout: include/mysti_verify.h, mv_connect_blocks).
+pub struct Connected {
+    pub accepted: Accepted,  // blk_state: MV_ACC_SUSPENDED for the blocks that wait in the store
+    pub connected: Vec<u64>, // eight words per row, in causal order: the reference, the block's index
+                             // in this call or u64::MAX (an earlier call suspended it), its level
 }
 
 /// Result of `GpuVerifier::accept_blocks` (layout: include/mysti_verify.h, mv_accept_blocks).
