@@ -80,42 +80,57 @@ MV_DEV void fe_neg(fe& r, const fe& a) {
   fe_sub(r, z, a);
 }
 
-// Column-scanning reduction, shared by mul and sq. col(k) returns the 64-bit sum
-// of column k (< 2^63.3). A high column k = 9..16 is folded as it is produced,
-// without a carry chain: its 32-bit halves L, H go to the low columns with
-// 2^261 = 1216 and 2^(261+32) = 2^(29*10) * 8 = 1216 * 8 (mod p) as one
-// v_mad_u64_u32 each (L * 1216 -> column k-9, H * 9728 -> column k-8; the low
-// sums stay < 2^63.3 + 2^42.3 + 2^44.6). Only the 9 low sums are live at a time.
+// c += x * y as one link of a column's v_mad_u64_u32 chain. Opaque after every link: the
+// compiler otherwise sums a column's products apart from the carry the chain started from and
+// joins the two with a 64-bit add (it moves the value computed last to the end of a sum), and
+// may rebuild a low half from v_mul_lo_u32 products.
+MV_DEV void fe_mac(uint64_t& c, uint32_t x, uint32_t y) {
+  c += (uint64_t)x * y;
+  asm("" : "+v"(c));
+}
+
+// Column-scanning reduction, shared by mul and sq. col(k, c) returns c plus the 64-bit sum
+// of column k (< 2^63.3), as fe_mac links. The high columns k = 9..16 come first, as
+// independent chains with no carry between them: the 32-bit halves L, H of each go to the low
+// columns with 2^261 = 1216 and 2^(261+32) = 2^(29*10) * 8 = 1216 * 8 (mod p) as one
+// v_mad_u64_u32 each (L * 1216 -> column k-9, H * 9728 -> column k-8). The low columns
+// k = 0..8 follow in order, each ONE chain that starts from the previous column's carry (the
+// MAD's 64-bit addend takes it, so the ripple costs no 64-bit add of its own), then takes its
+// two fold terms and its products. A carry is a chain >> 29 < 2^35, so for N or A inputs a
+// chain stays < 2^63.3 + 2^44.6 + 2^42.3 + 2^35 < 2^64: the same integers as summing every
+// column first and rippling afterwards, in another association, so every output limb is what
+// that order gives.
 template <class Col>
 MV_DEV void fe_reduce_scan(fe& r, Col col) {
-  uint64_t lo[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) lo[k] = col(k);
+  uint32_t L[8], H[8];
 #pragma unroll
   for (int k = 9; k < 17; k++) {
-    uint64_t c = col(k);
-    // opaque: keeps the column one 64-bit MAD chain (otherwise the compiler may also
-    // rebuild its low half from v_mul_lo_u32 products for the L * 1216 term)
-    asm("" : "+v"(c));
-    lo[k - 9] += (uint64_t)(uint32_t)c * R261;
-    lo[k - 8] += (uint64_t)(uint32_t)(c >> 32) * (8 * R261);
+    const uint64_t c = col(k, 0);
+    L[k - 9] = (uint32_t)c;
+    H[k - 9] = (uint32_t)(c >> 32);
   }
+  uint32_t o[9];  // (r may be an operand: written once every column has read its limbs)
+  uint64_t carry = 0;
 #pragma unroll
-  for (int k = 0; k < 8; k++) {
-    r.v[k] = (uint32_t)lo[k] & M29;
-    lo[k + 1] += lo[k] >> 29;
+  for (int k = 0; k < 9; k++) {
+    uint64_t c = carry;
+    if (k < 8) fe_mac(c, L[k & 7], R261);
+    if (k > 0) fe_mac(c, H[(k + 7) & 7], 8 * R261);
+    c = col(k, c);
+    o[k] = (uint32_t)c & M29;
+    carry = c >> 29;
   }
-  r.v[8] = (uint32_t)lo[8] & M29;
-  uint64_t t0 = (uint64_t)r.v[0] + (lo[8] >> 29) * R261;  // top < 2^35
-  r.v[0] = (uint32_t)t0 & M29;
-  r.v[1] += (uint32_t)(t0 >> 29);  // < 2^29 + 2^17
+  uint64_t t0 = (uint64_t)o[0] + carry * R261;  // top < 2^35
+  o[0] = (uint32_t)t0 & M29;
+  o[1] += (uint32_t)(t0 >> 29);  // < 2^29 + 2^17
+#pragma unroll
+  for (int k = 0; k < 9; k++) r.v[k] = o[k];
 }
 
 MV_DEV void fe_mul(fe& r, const fe& a, const fe& b) {
-  fe_reduce_scan(r, [&](int k) {
-    uint64_t c = 0;
+  fe_reduce_scan(r, [&](int k, uint64_t c) {
 #pragma unroll
-    for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) c += (uint64_t)a.v[i] * b.v[k - i];
+    for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) fe_mac(c, a.v[i], b.v[k - i]);
     return c;
   });
 }
@@ -131,10 +146,10 @@ MV_DEV void fe_sq(fe& r, const fe& a_in) {
   uint32_t a2[9];
 #pragma unroll
   for (int i = 0; i < 9; i++) a2[i] = a.v[i] << 1;  // < 2^31.01
-  fe_reduce_scan(r, [&](int k) {
-    uint64_t c = (k & 1) ? 0 : (uint64_t)a.v[k >> 1] * a.v[k >> 1];
+  fe_reduce_scan(r, [&](int k, uint64_t c) {
+    if (!(k & 1)) fe_mac(c, a.v[k >> 1], a.v[k >> 1]);
 #pragma unroll
-    for (int i = (k > 8 ? k - 8 : 0); i < k - i; i++) c += (uint64_t)a2[i] * a.v[k - i];
+    for (int i = (k > 8 ? k - 8 : 0); i < k - i; i++) fe_mac(c, a2[i], a.v[k - i]);
     return c;
   });
 }

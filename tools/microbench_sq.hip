@@ -18,10 +18,23 @@
 // (373 against 203 slots) and 2.7x on a lone wave's chain, fe25 1.24x (252 slots) and 1.2x, so
 // the 9 x 29 form stays. The chains start from the same values; their results are compared mod p
 // (canonical encodings).
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I mysticeti_amd/csrc tools/microbench_sq.hip -o tools/microbench_sq
+//
+//   fe29r the 9 x 29 form in the order fe_sq had before the carry went through the MAD addend
+//         (kept here as sq29_ripple): every column summed on its own, independent of the others,
+//         then the ripple lo[k + 1] += lo[k] >> 29 as eight 64-bit adds. fe_sq's low columns are
+//         ONE dependent chain of ~60 MADs instead, eight half-rate instructions shorter.
+//
+// `microbench_sq occ` times fe29r against fe29 at 2, 3 and 4 waves per SIMD (cus * W workgroups
+// of 4 waves), REPS times each in turns, one JSON line per run and a summary line per
+// occupancy (profiles/fe_carry/microbench_sq.jsonl): whether the longer chain costs throughput at
+// the occupancies k_bv_prep and k_bv_bucket_bal run at. Raw limbs of both must agree.
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -mllvm -amdgpu-sched-strategy=max-ilp -I mysticeti_amd/csrc \
+//         tools/microbench_sq.hip -o tools/microbench_sq      (batch.hip's scheduler)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include "asm_ops.h"
 #include "fe25519.h"
@@ -35,6 +48,44 @@ using namespace mv;
       return 1;                                                         \
     }                                                                   \
   } while (0)
+
+// ---- 9 x 29, columns first, ripple afterwards (fe_sq's order before the carry-in-addend form) ----
+MV_DEV void sq29_ripple(fe& r, const fe& a_in) {
+  fe a;
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    a.v[i] = a_in.v[i];
+    asm("" : "+v"(a.v[i]));
+  }
+  uint32_t a2[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) a2[i] = a.v[i] << 1;
+  auto col = [&](int k) {
+    uint64_t c = (k & 1) ? 0 : (uint64_t)a.v[k >> 1] * a.v[k >> 1];
+#pragma unroll
+    for (int i = (k > 8 ? k - 8 : 0); i < k - i; i++) c += (uint64_t)a2[i] * a.v[k - i];
+    return c;
+  };
+  uint64_t lo[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) lo[k] = col(k);
+#pragma unroll
+  for (int k = 9; k < 17; k++) {
+    uint64_t c = col(k);
+    asm("" : "+v"(c));
+    lo[k - 9] += (uint64_t)(uint32_t)c * R261;
+    lo[k - 8] += (uint64_t)(uint32_t)(c >> 32) * (8 * R261);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    r.v[k] = (uint32_t)lo[k] & M29;
+    lo[k + 1] += lo[k] >> 29;
+  }
+  r.v[8] = (uint32_t)lo[8] & M29;
+  uint64_t t0 = (uint64_t)r.v[0] + (lo[8] >> 29) * R261;
+  r.v[0] = (uint32_t)t0 & M29;
+  r.v[1] += (uint32_t)(t0 >> 29);
+}
 
 // ---- 8 x 32: r = a^2 mod p, a < 2^256 in, r < 2^256 out (not canonical) ----
 MV_DEV void sq32(uint32_t (&r)[8], const uint32_t (&a)[8]) {
@@ -212,6 +263,25 @@ __global__ void __launch_bounds__(256) k_sq29(uint32_t* out, int iters, unsigned
   if (threadIdx.x == 0) atomicMax(cyc, (unsigned long long)(t1 - t0));
 }
 
+// the occupancy sweep's kernels: raw limbs out (9 words per lane), so the two orders are compared bit for bit
+template <bool RIPPLE>
+__global__ void __launch_bounds__(256) k_sq29_raw(uint32_t* out, int iters, unsigned long long* cyc) {
+  uint32_t a32[8];
+  fe a;
+  start(a32, a, blockIdx.x * blockDim.x + threadIdx.x);
+  const uint64_t t0 = __builtin_amdgcn_s_memtime();
+#pragma unroll 1
+  for (int it = 0; it < iters; it++) {
+    if (RIPPLE) sq29_ripple(a, a);
+    else fe_sq(a, a);
+  }
+  const uint64_t t1 = __builtin_amdgcn_s_memtime();
+  const size_t g = blockIdx.x * blockDim.x + threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 9; i++) out[9 * g + i] = a.v[i];
+  if (threadIdx.x == 0) atomicMax(cyc, (unsigned long long)(t1 - t0));
+}
+
 __global__ void __launch_bounds__(256) k_sq32(uint32_t* out, int iters, unsigned long long* cyc) {
   uint32_t a[8];
   fe a29;
@@ -269,9 +339,63 @@ int run(const char* name, kfn k, int blocks, int iters, uint32_t* d, unsigned lo
   return 0;
 }
 
-int main() {
+// fe29r against fe29 at 2, 3 and 4 waves per SIMD
+int occupancy_sweep(int cus) {
+  const int iters = 1 << 16, REPS = 5;  // ~30 ms a run: past the clock ramp of a cold start
+  const size_t lanes_max = (size_t)cus * 4 * 256;
+  uint32_t *dr, *dn;
+  unsigned long long* dc;
+  CHECK(hipMalloc(&dr, lanes_max * 36));
+  CHECK(hipMalloc(&dn, lanes_max * 36));
+  CHECK(hipMalloc(&dc, 8));
+  uint32_t* hr = (uint32_t*)malloc(lanes_max * 36);
+  uint32_t* hn = (uint32_t*)malloc(lanes_max * 36);
+  size_t bad = 0;
+  for (int w = 2; w <= 4; w++) {
+    const int blocks = cus * w;
+    const double sq = (double)blocks * 256 * iters;
+    double lo[2] = {1e30, 1e30}, hi[2] = {0, 0}, all[2][8];
+    for (int rep = 0; rep < REPS; rep++)
+      for (int f = 0; f < 2; f++) {
+        double us, cyc;
+        if (run("", f ? k_sq29_raw<false> : k_sq29_raw<true>, blocks, iters, f ? dn : dr, dc, &us, &cyc)) return 1;
+        const double slots = (cyc / 2.0) / (sq / (cus * 4.0) / 64.0);
+        printf("{\"form\": \"%s\", \"waves_per_simd\": %d, \"rep\": %d, \"us\": %.1f, \"sq_per_s\": %.4g, "
+               "\"clock_GHz\": %.3f, \"issue_slots_per_sq\": %.1f}\n",
+               f ? "fe29 (fe_sq, carry in the MAD addend)" : "fe29r (columns, then ripple)", w, rep, us,
+               sq / (us * 1e-6), cyc / (us * 1e3), slots);
+        all[f][rep] = us;
+        lo[f] = us < lo[f] ? us : lo[f];
+        hi[f] = us > hi[f] ? us : hi[f];
+      }
+    double med[2];
+    for (int f = 0; f < 2; f++) {  // median of REPS
+      for (int i = 0; i < REPS; i++)
+        for (int j = i + 1; j < REPS; j++)
+          if (all[f][j] < all[f][i]) {
+            const double t = all[f][i];
+            all[f][i] = all[f][j];
+            all[f][j] = t;
+          }
+      med[f] = all[f][REPS / 2];
+    }
+    printf("{\"summary_waves_per_simd\": %d, \"fe29r_us_min_med_max\": [%.1f, %.1f, %.1f], "
+           "\"fe29_us_min_med_max\": [%.1f, %.1f, %.1f], \"fe29r_spread_pct\": %.2f, \"fe29_gain_pct\": %.2f}\n",
+           w, lo[0], med[0], hi[0], lo[1], med[1], hi[1], 100.0 * (hi[0] - lo[0]) / med[0],
+           100.0 * (med[0] - med[1]) / med[0]);
+    const size_t words = (size_t)blocks * 256 * 9;
+    CHECK(hipMemcpy(hr, dr, words * 4, hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(hn, dn, words * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < words; i++) bad += hr[i] != hn[i];
+  }
+  printf("{\"raw_limbs_agree\": %s, \"mismatched_words\": %zu}\n", bad ? "false" : "true", bad);
+  return bad != 0;
+}
+
+int main(int argc, char** argv) {
   int cus = 0;
   CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+  if (argc > 1 && !strcmp(argv[1], "occ")) return occupancy_sweep(cus);
   const int iters = 4096;
   const int full_blocks = cus * 8;  // 256-thread blocks: 4 waves each, 8 waves per SIMD
   uint32_t *d29, *d32, *d25;
