@@ -51,6 +51,11 @@
  *   mv_connect_blocks      mv_accept_blocks and the suspend / unlock cascade of add_blocks (block_manager.rs:102-131)
  *                          over a store of suspended blocks in device memory: the blocks the core may process,
  *                          in a causal order
+ *   mv_dag_*, mv_decide_leaders   the edges of the blocks mv_connect_blocks stored, kept in device memory, and
+ *                          BaseCommitter::try_direct_decide (consensus/base_committer.rs:323-357) over them at
+ *                          the production wave length 3, which UniversalCommitter::try_commit
+ *                          (consensus/universal_committer.rs:30-90) runs for every undecided leader after
+ *                          every add_blocks
  *
  * Conventions
  *   - The caller owns every buffer passed in and out; they must stay valid for the call.
@@ -487,6 +492,76 @@ mv_status mv_pending_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t includes);
  * (that connected something) of the last connect call. */
 mv_status mv_pending_stats(mv_ctx* ctx, uint64_t* out /* 4 */);
 
+/* ---- the DAG store and the direct decision rule ----
+ * Opt-in: after mv_dag_reserve, mv_connect_blocks (and its device-buffer variant) copies every block
+ * it connects -- the slot of its reference, its (authority, round), its includes as slots of the
+ * index -- into the context's DAG store before the suspended-block store drops it. Records stand in
+ * the order blocks became MV_REF_STORED: the connected-row order, call after call. Without the
+ * reserve, mv_connect_blocks does what it did before, launch for launch. The store grows
+ * geometrically, also under the device-buffer connect call (which synchronises anyway);
+ * mv_index_clear empties it, mv_destroy frees it, a rebuild of the index re-resolves its slots.
+ * References seeded with mv_index_insert_stored / mv_dev_index_insert (genesis, a replay's rows)
+ * have no record: seeding edges is out of scope. That is safe because the rule below is monotone
+ * in the records (see mv_decide_leaders). */
+mv_status mv_dag_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t includes);
+/* Drops the records of rounds below `round` by stable compaction: BlockStore::cleanup /
+ * unload_below_round (block_store.rs:207-218, 374-390) for this store. The index entries stay
+ * (a state never falls); an include whose record was pruned reads "no record", like one that
+ * never had any. MV_E_INVALID_ARG without a store. */
+mv_status mv_dag_prune(mv_ctx* ctx, uint64_t round);
+/* out[0] records, out[1] their includes, out[2] the lowest and out[3] the highest round of a record
+ * (both 0 without records). All 0 without a store. */
+mv_status mv_dag_stats(mv_ctx* ctx, uint64_t* out /* 4 */);
+
+#define MV_LEADER_UNDECIDED 0 /* LeaderStatus::Undecided: neither rule holds on the records there are */
+#define MV_LEADER_COMMIT 1    /* LeaderStatus::Commit(block): words 0-5 are the block's reference */
+#define MV_LEADER_SKIP 2      /* LeaderStatus::Skip: a quorum of blame (base_committer.rs:326-329) */
+#define MV_LEADER_CONFLICT 3  /* more than one leader block with enough support: the reference panics (:347-352) */
+#define MV_LEADER_OVERFLOW 4  /* more than MV_DECIDE_MAX_LEADER_BLOCKS leader blocks: not a verdict, the caller
+                                 decides this leader itself */
+#define MV_DECIDE_MAX_LEADER_BLOCKS 8
+/* BaseCommitter::try_direct_decide (base_committer.rs:323-357) at wave length 3 (core.rs:127-129 never
+ * calls with_wave_length; DEFAULT_WAVE_LENGTH = MINIMUM_WAVE_LENGTH = 3), for each of n leader rows
+ * (authority a, round r) on its own. The caller elects the leaders (Committee::elect_leader,
+ * committee.rs:137-147, is host logic). The stored blocks are the DAG store's records; a quorum is
+ * stake > quorum_threshold (committee.rs:125-127). A verified block's includes all have a lower
+ * round than the block (threshold_clock.rs:18-22), so find_support (:109-134) never recurses here.
+ *   Voting blocks: the records of round r + 1. Decision blocks: those of round r + 2. Leader
+ *   blocks: those with (authority, round) = (a, r).
+ *   Blame (enough_leader_blame, :228-249): the authors of voting blocks none of whose includes has
+ *   authority a -- the authority only, never the round (:234-237). A quorum of them: MV_LEADER_SKIP.
+ *   The support of a voting block V: the first include of V, in include order, with (authority,
+ *   round) = (a, r), or none. V votes for leader block B when that include is B's reference (is_vote, :138-145).
+ *   A decision block C is a certificate for B (is_certificate, :152-180) when the authors of those
+ *   includes of C that have a record, are of round r + 1 and vote for B are a quorum; an author
+ *   counts once, however many of its blocks C includes.
+ *   B has enough support (enough_leader_support, :253-289) when the authors of its certificates are
+ *   a quorum. (The total_stake quick reject of :261-273 cannot change a result and is left out.)
+ *   Exactly one leader block with enough support: MV_LEADER_COMMIT. More than one:
+ *   MV_LEADER_CONFLICT. None: MV_LEADER_UNDECIDED. The blame test comes first, as in the reference.
+ *   More than MV_DECIDE_MAX_LEADER_BLOCKS leader blocks, and no quorum of blame: MV_LEADER_OVERFLOW.
+ * out row i: words 0-5 the committed block's reference (else a, r and four zero words), 6 the
+ * status, 7 the leader blocks found. stakes row i (stakes may be NULL): the blame stake; the vote
+ * stake -- the distinct authors of voting blocks that vote for the block -- of the one block with
+ * enough support, else of the leader block with the largest (vote stake, certificate stake) pair;
+ * the certificate stake of that same block. They are whole sums without early exit. Both are 0
+ * under more than MV_DECIDE_MAX_LEADER_BLOCKS leader blocks.
+ * A row whose authority is not in the committee is MV_LEADER_UNDECIDED with 0 leader blocks and 0
+ * stakes. A leader whose round lies below the store's lowest record round (or any, in an empty
+ * store) is MV_LEADER_UNDECIDED.
+ * Monotone: a block without a record can only lower a stake. So a store that lacks edges (seeded
+ * references, pruned rounds, blocks still suspended) turns COMMIT or SKIP into UNDECIDED, never the
+ * reverse, and never one COMMIT into another. (Where authors of more than a third of the stake
+ * equivocate in the voting round, a quorum of blame can stand beside a leader block with enough
+ * support; blame is tested first, here as in the reference, so fewer records can uncover that COMMIT.)
+ * What stays with the caller: try_indirect_decide (:294-318), the longest-decided-prefix rule and
+ * the genesis filter of UniversalCommitter::try_commit, and the linearizer.
+ * Requires mv_set_committee (MV_E_NO_COMMITTEE) and mv_dag_reserve (MV_E_INVALID_ARG without the
+ * store). n = 0 does nothing. Results do not depend on MV_INDEX_TAG_BITS, on the order blocks were
+ * delivered in, or on launch geometry. */
+mv_status mv_decide_leaders(mv_ctx* ctx, const uint64_t* leaders /* n x 2: authority, round */, uint32_t n,
+                            uint64_t* out /* n x 8 */, uint64_t* stakes /* n x 3, may be NULL */);
+
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
  * library's stream for that device). They enqueue work and return without synchronising. */
@@ -579,6 +654,10 @@ mv_status mv_dev_connect_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, u
                                 uint8_t* d_blk_status, uint8_t* d_blk_state, uint64_t* d_missing, uint64_t cap_missing,
                                 uint64_t* n_missing, uint64_t* d_connected, uint64_t cap_connected,
                                 uint64_t* n_connected, void* stream);
+/* mv_decide_leaders with the leader rows and the results in HBM of the context's first device.
+ * The rows are read back to be sorted by round; `stream` is synchronised. */
+mv_status mv_dev_decide_leaders(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_out,
+                                uint64_t* d_stakes /* may be NULL */, void* stream);
 /* crc32fast::hash of n strings of device buffer d_buf at d_off/d_len (device arrays) -> d_out. Enqueue only. */
 mv_status mv_dev_crc32(mv_ctx* ctx, int device, const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len,
                        uint32_t n, uint32_t* d_out, void* stream);

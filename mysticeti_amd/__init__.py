@@ -33,6 +33,9 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.connect_blocks    accept_blocks and the suspend / unlock cascade of add_blocks
                            (block_manager.rs:102-131) over a store of suspended blocks in device memory:
                            the blocks the core may process, in a causal order
+  Engine.dag_reserve, Engine.dag_prune, Engine.dag_stats, Engine.decide_leaders (and dev_decide_leaders)
+                           the edges of the blocks connect_blocks stored, kept on the GPU, and
+                           BaseCommitter::try_direct_decide over them (base_committer.rs:323-357)
   Engine.dev_accept_blocks, Engine.dev_connect_blocks, Engine.dev_index_insert
                            the same on buffers already in HBM (a replay's rows go in at a stride)
   frame_messages           the frame and message walk alone, on the host, for one stream
@@ -72,6 +75,7 @@ EXPORTS = [
     "mv_index_reserve", "mv_index_clear", "mv_index_stats", "mv_index_insert", "mv_index_lookup", "mv_index_wanted",
     "mv_accept_blocks", "mv_dev_accept_blocks", "mv_dev_index_insert",
     "mv_index_insert_stored", "mv_connect_blocks", "mv_dev_connect_blocks", "mv_pending_reserve", "mv_pending_stats",
+    "mv_dag_reserve", "mv_dag_prune", "mv_dag_stats", "mv_decide_leaders", "mv_dev_decide_leaders",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
@@ -89,6 +93,11 @@ ACC_STATE = ["REJECTED", "NEW", "KNOWN", "DUP", "DROPPED", "SUSPENDED"]
 ACC_REJECTED, ACC_NEW, ACC_KNOWN, ACC_DUP, ACC_DROPPED, ACC_SUSPENDED = range(6)
 CONNECT_EARLIER = 0xFFFFFFFFFFFFFFFF  # word 6 of a connected row: an earlier call suspended the block
 E_INDEX_FULL = -6
+E_INVALID_ARG, E_NO_COMMITTEE = -1, -4
+# mv_decide_leaders: word 6 of a row, and the leader blocks a row can tell apart
+LEADER_STATUS = ["UNDECIDED", "COMMIT", "SKIP", "CONFLICT", "OVERFLOW"]
+LEADER_UNDECIDED, LEADER_COMMIT, LEADER_SKIP, LEADER_CONFLICT, LEADER_OVERFLOW = range(5)
+DECIDE_MAX_LEADER_BLOCKS = 8
 WAL_MAP_BITS, WAL_MAP_BITS_TEST = 24, 16  # wal.rs:95-103
 # batch path stages, the block pipeline's, the WAL replay's (mv_stage_times order, MV_NSTAGES)
 STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "hash", "verify", "verdict", "wal_walk",
@@ -186,6 +195,11 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_connect_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, vp, u32, vp, vp, vp, u64, vp, vp, u64, vp, vp]
     lib.mv_pending_reserve.argtypes = [vp, u64, u64]
     lib.mv_pending_stats.argtypes = [vp, vp]
+    lib.mv_dag_reserve.argtypes = [vp, u64, u64]
+    lib.mv_dag_prune.argtypes = [vp, u64]
+    lib.mv_dag_stats.argtypes = [vp, vp]
+    lib.mv_decide_leaders.argtypes = [vp, vp, u32, vp, vp]
+    lib.mv_dev_decide_leaders.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     lib.mv_host_free.argtypes = [vp, vp]
     lib.mv_host_free.restype = None
@@ -783,6 +797,37 @@ class Engine:
         self._suspended = int(out[1])
         return PendingStats(*(int(x) for x in out))
 
+    def dag_reserve(self, blocks: int, includes: int):
+        """Turns the DAG store on (mv_dag_reserve), with room for `blocks` records and `includes`
+        includes in all: from now on connect_blocks keeps the edges of what it connects."""
+        self._check(self.lib.mv_dag_reserve(self.ctx, int(blocks), int(includes)), "mv_dag_reserve")
+
+    def dag_prune(self, round: int):
+        """Drops the records of rounds below `round` (mv_dag_prune)."""
+        self._check(self.lib.mv_dag_prune(self.ctx, int(round)), "mv_dag_prune")
+
+    def dag_stats(self) -> "DagStats":
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.mv_dag_stats(self.ctx, _p(out)), "mv_dag_stats")
+        return DagStats(*(int(x) for x in out))
+
+    def decide_leaders(self, leaders) -> "Decided":
+        """The direct decision rule (mv_decide_leaders) for every (authority, round) of `leaders`."""
+        rows = np.ascontiguousarray(np.asarray(leaders, dtype=np.uint64).reshape(-1, 2))
+        n = rows.shape[0]
+        out, stakes = np.zeros((n, 8), dtype=np.uint64), np.zeros((n, 3), dtype=np.uint64)
+        self._check(self.lib.mv_decide_leaders(self.ctx, _p(rows) if n else None, n, _p(out) if n else None,
+                                               _p(stakes) if n else None), "mv_decide_leaders")
+        return Decided(out, stakes)
+
+    def dev_decide_leaders(self, device: int, d_leaders, d_out, d_stakes=None, stream_handle: int = 0):
+        """mv_dev_decide_leaders on torch device tensors: d_leaders (n, 2), d_out (n, 8), d_stakes
+        (n, 3) or None, all int64."""
+        vp = ctypes.c_void_p
+        ptr = lambda t: vp(t.data_ptr()) if t is not None else None
+        self._check(self.lib.mv_dev_decide_leaders(self.ctx, device, ptr(d_leaders), d_leaders.shape[0], ptr(d_out),
+                                                   ptr(d_stakes), vp(stream_handle or None)), "mv_dev_decide_leaders")
+
     def dev_index_insert(self, device: int, d_words, stride_words: int, n: int, state: int = REF_HAVE,
                          stream_handle: int = 0, word_offset: int = 0):
         """mv_dev_index_insert: reference i is the six int64 words of torch device tensor d_words at
@@ -1004,6 +1049,31 @@ class PendingStats:
 
     def __init__(self, stored, suspended, includes, levels):
         self.stored, self.suspended, self.includes, self.levels = stored, suspended, includes, levels
+
+
+class DagStats:
+    """Result of Engine.dag_stats (mv_dag_stats): records, their includes, the lowest and the
+    highest round of a record."""
+
+    def __init__(self, records, includes, lowest_round, highest_round):
+        self.records, self.includes, self.lowest_round, self.highest_round = records, includes, lowest_round, highest_round
+
+
+class Decided:
+    """Result of Engine.decide_leaders (mv_decide_leaders): rows (n, 8) uint64 -- words 0-5 the
+    committed reference, 6 the LEADER_* status, 7 the leader blocks found -- and stakes (n, 3):
+    blame, vote and certificate stake."""
+
+    def __init__(self, rows, stakes):
+        self.rows, self.stakes = rows, stakes
+        self.status = rows[:, 6].astype(np.int64)
+        self.leader_blocks = rows[:, 7].astype(np.int64)
+
+    def ref(self, i: int):
+        """(authority, round, digest) of row i's committed block, None unless LEADER_COMMIT."""
+        if int(self.rows[i, 6]) != LEADER_COMMIT:
+            return None
+        return int(self.rows[i, 0]), int(self.rows[i, 1]), self.rows[i, 2:6].astype("<u8").tobytes()
 
 
 class WalReplay:

@@ -22,6 +22,17 @@ constexpr int kMaxRounds = 1 << 16;
 
 using Index = Device::Index;
 using Pending = Device::Index::Pending;
+using Dag = Device::Index::Dag;
+constexpr uint64_t kMaxDagRecords = 0xfffffffeull;  // the slot -> record map holds a u32, all ones: no record
+constexpr uint64_t kMaxDecideWaves = 1ull << 26;
+
+// the DAG store as the kernels see it: slot | round | ibase (u64 each) | auth | kc (u32 each)
+mvk::DagStore dag_view(const Dag& dg, const DevBuf& rec, const DevBuf& inc, uint64_t cap_b, uint64_t cap_i) {
+  char* b = rec.as<char>();
+  return mvk::DagStore{(uint64_t*)b, (uint64_t*)(b + 8 * cap_b), (uint32_t*)(b + 24 * cap_b), (uint64_t*)(b + 16 * cap_b),
+                       (uint32_t*)(b + 28 * cap_b), inc.as<uint64_t>(), dg.map.as<uint32_t>(), cap_b, cap_i, dg.map_slots};
+}
+mvk::DagStore dag_view(const Dag& dg) { return dag_view(dg, dg.rec, dg.inc, dg.cap_b, dg.cap_i); }
 
 // copy k of the suspended-block store as the kernels see it
 mvk::PendStore pend_view(const Pending& pd, int k) {
@@ -97,8 +108,31 @@ mv_status index_resize(mv_ctx* ctx, Device& dev, uint64_t slots, hipStream_t s) 
       HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, p.slot, pd.nb, ix.ctl.as<uint64_t>(), s));
       HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, p.inc, pd.ni, ix.ctl.as<uint64_t>(), s));
     }
+    // ... and so does the DAG store
+    const Dag& dg = ix.dag;
+    if (dg.on && dg.nb) {
+      const mvk::DagStore d = dag_view(dg);
+      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, d.slot, dg.nb, ix.ctl.as<uint64_t>(), s));
+      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, d.inc, dg.ni, ix.ctl.as<uint64_t>(), s));
+    }
+  }
+  // its slot -> record map is as long as the table: a fresh one, filled from the re-resolved slots
+  DevBuf fresh_map;
+  if (ix.dag.on) {
+    if (fresh_map.ensure(4 * (size_t)slots) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(s);
+      return set_err(ctx, MV_E_ALLOC, "no device memory for the DAG store's map");
+    }
+    mvk::DagStore d = dag_view(ix.dag);
+    d.map = fresh_map.as<uint32_t>(), d.n_slots = slots;
+    HIPCHK(ctx, mvk::launch_dag_map(d, ix.dag.nb, ix.ctl.as<uint64_t>(), s));
   }
   HIPCHK(ctx, hipStreamSynchronize(s));  // the old table is read until here; `fresh` frees it below
+  if (ix.dag.on) {
+    std::swap(ix.dag.map, fresh_map);
+    ix.dag.map_slots = slots;
+  }
   std::swap(ix.tab, fresh);
   ix.slots = slots;
   ix.tag_bits = bits;
@@ -186,6 +220,36 @@ mv_status pending_room(mv_ctx* ctx, Device& dev, uint64_t more_b, uint64_t more_
   }
   pd.cur = 0;
   pd.cap_b = fresh.cap_b, pd.cap_i = fresh.cap_i;
+  return MV_OK;
+}
+
+// Room in the DAG store for more_b records and more_i includes on top of those there: a fresh copy,
+// at least twice as large, takes the records over. Synchronises s when it grows.
+mv_status dag_room(mv_ctx* ctx, Device& dev, uint64_t more_b, uint64_t more_i, hipStream_t s) {
+  Dag& dg = dev.index.dag;
+  const uint64_t need_b = dg.nb + more_b, need_i = dg.ni + more_i;
+  if (need_b <= dg.cap_b && need_i <= dg.cap_i) return MV_OK;
+  if (need_b > kMaxDagRecords || need_i > (1ull << 40)) return set_err(ctx, MV_E_INVALID_ARG, "too many records in the DAG store");
+  const uint64_t cap_b = need_b > dg.cap_b ? std::max<uint64_t>(need_b, 2 * dg.cap_b) : dg.cap_b;
+  const uint64_t cap_i = need_i > dg.cap_i ? std::max<uint64_t>(need_i, 2 * dg.cap_i) : dg.cap_i;
+  DevBuf rec, inc;
+  if (rec.ensure(32 * (size_t)cap_b) != hipSuccess || inc.ensure(8 * (size_t)cap_i) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(ctx, MV_E_ALLOC, "no device memory for the DAG store");
+  }
+  if (dg.nb) {
+    const mvk::DagStore from = dag_view(dg), to = dag_view(dg, rec, inc, cap_b, cap_i);
+    HIPCHK(ctx, hipMemcpyAsync(to.slot, from.slot, 8 * (size_t)dg.nb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(to.round, from.round, 8 * (size_t)dg.nb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(to.ibase, from.ibase, 8 * (size_t)dg.nb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(to.auth, from.auth, 4 * (size_t)dg.nb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(to.kc, from.kc, 4 * (size_t)dg.nb, hipMemcpyDeviceToDevice, s));
+    if (dg.ni) HIPCHK(ctx, hipMemcpyAsync(to.inc, from.inc, 8 * (size_t)dg.ni, hipMemcpyDeviceToDevice, s));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(s));  // the old copy is read until here; rec and inc free it below
+  std::swap(dg.rec, rec);
+  std::swap(dg.inc, inc);
+  dg.cap_b = cap_b, dg.cap_i = cap_i;
   return MV_OK;
 }
 
@@ -366,7 +430,7 @@ mv_status connect_sweep(mv_ctx* ctx, Device& dev, const AcceptOut& ao, uint64_t*
   if (st != MV_OK) return st;
   uint64_t* ctl = ix.ctl.as<uint64_t>();
   const uint64_t* h = nullptr;
-  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_PB_NB, 0, 8 * (mvk::IX_CTL_WORDS - mvk::IX_CTL_PB_NB), s));
+  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_PB_NB, 0, 8 * (mvk::IX_CTL_PB_END - mvk::IX_CTL_PB_NB), s));
   if (ao.ncand) {  // (accept_run made room for ncand blocks and ninc includes)
     const size_t w64 = 8 * mvk::index_groups(ao.ncand);
     HIPCHK(ctx, ix.wg.ensure(4 * w64));
@@ -388,6 +452,9 @@ mv_status connect_sweep(mv_ctx* ctx, Device& dev, const AcceptOut& ao, uint64_t*
   HIPCHK(ctx, pd.hit.ensure((size_t)nb));
   HIPCHK(ctx, pd.newbase.ensure(8 * (size_t)nb));
   HIPCHK(ctx, hipMemsetAsync(pd.lvl.p, 0, 4 * (size_t)nb, s));
+  Dag& dg = ix.dag;
+  if (dg.on) HIPCHK(ctx, pd.row_of.ensure(4 * (size_t)nb));
+  uint32_t* row_of = dg.on ? pd.row_of.as<uint32_t>() : nullptr;
   // the sweep: levels are enqueued 2, 4, 8, then 16 at a time and their counts read together; a
   // level past the fixed point lists nothing. At most nb levels connect something.
   uint64_t level = 0;
@@ -396,7 +463,7 @@ mv_status connect_sweep(mv_ctx* ctx, Device& dev, const AcceptOut& ao, uint64_t*
     const int m = (int)std::min<uint64_t>(ahead, nb + 1 - level);
     for (int k = 0; k < m; k++)
       HIPCHK(ctx, mvk::launch_pend_level(t, p, nb, pd.lvl.as<uint32_t>(), pd.hit.as<uint8_t>(), level + k,
-                                         ix.wg.as<uint64_t>(), d_rows, cap, ctl, mvk::IX_CTL_LV0 + k, s));
+                                         ix.wg.as<uint64_t>(), d_rows, cap, ctl, mvk::IX_CTL_LV0 + k, row_of, s));
     st = read_ctl(ctx, dev, s, &h);
     if (st != MV_OK) return st;
     int k = 0;
@@ -407,6 +474,17 @@ mv_status connect_sweep(mv_ctx* ctx, Device& dev, const AcceptOut& ao, uint64_t*
   }
   pd.levels = level;
   *n_connected = h[mvk::IX_CTL_PB_ROWS];
+  // with a DAG store: the rows' records join it, in row order, before the compaction drops them
+  // (the includes they bring are at most those the suspended-block store holds)
+  const uint64_t dag_rows = dg.on ? std::min<uint64_t>(h[mvk::IX_CTL_PB_ROWS], nb) : 0, dag_ni_cap = pd.ni;
+  if (dag_rows) {
+    st = dag_room(ctx, dev, dag_rows, pd.ni, s);
+    if (st != MV_OK) return st;
+    HIPCHK(ctx, dg.src.ensure(8 * (size_t)dag_rows));
+    HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_DG_NI, 0, 8, s));
+    HIPCHK(ctx, mvk::launch_dag_append(t, p, nb, pd.lvl.as<uint32_t>(), row_of, dag_rows, dag_view(dg), dg.nb, dg.ni,
+                                       dg.src.as<uint64_t>(), ix.wg.as<uint64_t>(), ctl, s));
+  }
   // what stays is blocks_pending
   HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_PB_NB, 0, 16, s));
   HIPCHK(ctx, mvk::launch_pend_compact(t, p, q, nb, pd.newbase.as<uint64_t>(), ao.a.state, ao.a.n, ix.wg.as<uint64_t>(), ctl, s));
@@ -415,6 +493,70 @@ mv_status connect_sweep(mv_ctx* ctx, Device& dev, const AcceptOut& ao, uint64_t*
   pd.nb = std::min<uint64_t>(h[mvk::IX_CTL_PB_NB], nb);
   pd.ni = std::min<uint64_t>(h[mvk::IX_CTL_PB_NI], pd.ni);
   pd.cur ^= 1;
+  if (dag_rows) {
+    dg.nb += dag_rows;
+    dg.ni += std::min<uint64_t>(h[mvk::IX_CTL_DG_NI], dag_ni_cap);
+  }
+  return MV_OK;
+}
+
+// One decide call on stream s (include/mysti_verify.h, mv_decide_leaders): the rows sorted by round
+// on the host, k_dg_pick, the counts of voting and decision records read back (they size the
+// next launches), k_dg_vote, k_dg_cert, k_dg_decide. Results go to d_out / d_stakes (device).
+mv_status decide_run(mv_ctx* ctx, Device& dev, const uint64_t* leaders, uint32_t n32, uint64_t* d_out, uint64_t* d_stakes,
+                     hipStream_t s) {
+  Index& ix = dev.index;
+  Dag& dg = ix.dag;
+  const size_t n = n32;
+  mv_status st = index_ctl(ctx, dev, s);
+  if (st != MV_OK) return st;
+  uint64_t* ctl = ix.ctl.as<uint64_t>();
+  std::vector<uint32_t> order(n);
+  for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return leaders[2 * x + 1] < leaders[2 * y + 1]; });
+  // g_round (ng) | g_start (ng + 1) | l_auth | l_round | l_row (n each): laid out for ng = n, the most
+  std::vector<uint64_t> tab(5 * n + 1);
+  uint64_t *g_round = tab.data(), *g_start = g_round + n, *l_auth = g_start + n + 1, *l_round = l_auth + n, *l_row = l_round + n;
+  uint64_t ng = 0, gmax = 1;
+  for (size_t k = 0; k < n; k++) {
+    const uint64_t a = leaders[2 * (size_t)order[k]], r = leaders[2 * (size_t)order[k] + 1];
+    l_auth[k] = a, l_round[k] = r, l_row[k] = order[k];
+    if (ng == 0 || g_round[ng - 1] != r) g_round[ng] = r, g_start[ng] = k, ng++;
+    gmax = std::max<uint64_t>(gmax, k + 1 - g_start[ng - 1]);
+  }
+  g_start[ng] = n;
+  HIPCHK(ctx, dg.lead.ensure(8 * tab.size()));
+  HIPCHK(ctx, hipMemcpyAsync(dg.lead.p, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, s));
+  const uint64_t* dl = dg.lead.as<uint64_t>();
+  const mvk::DecideIn in{dl, dl + n, dl + 2 * n + 1, dl + 3 * n + 1, dl + 4 * n + 1, ng, n, gmax};
+  // per row: cand_slot (8 u64) | blame (16 u32) | vote (8 x 16) | cert (8 x 16) | cand_n
+  const size_t state_bytes = (64 + 4 * (size_t)(mvk::DG_BM_WORDS * 17 + 1)) * n;
+  HIPCHK(ctx, dg.state.ensure(state_bytes));
+  HIPCHK(ctx, hipMemsetAsync(dg.state.p, 0, state_bytes, s));
+  const uint64_t nb = dg.nb;
+  HIPCHK(ctx, dg.lists.ensure(12 * (size_t)nb + 4));
+  HIPCHK(ctx, ix.wg.ensure(4 * 8 * mvk::index_groups(nb) + 8));
+  mvk::DecideState ds{};
+  ds.cand_slot = dg.state.as<uint64_t>();
+  ds.blame = (uint32_t*)(ds.cand_slot + 8 * n);
+  ds.vote = ds.blame + mvk::DG_BM_WORDS * n;
+  ds.cert = ds.vote + 8 * mvk::DG_BM_WORDS * n;
+  ds.cand_n = ds.cert + 8 * mvk::DG_BM_WORDS * n;
+  ds.vpos = dg.lists.as<uint32_t>(), ds.vlist = ds.vpos + nb, ds.dlist = ds.vlist + nb;
+  const mvk::DagStore d = dag_view(dg);
+  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_DG_NVOTE, 0, 16, s));
+  HIPCHK(ctx, mvk::launch_decide_pick(d, nb, in, ds, ix.wg.as<uint64_t>(), ctl, s));
+  const uint64_t* h = nullptr;
+  st = read_ctl(ctx, dev, s, &h);
+  if (st != MV_OK) return st;
+  const uint64_t nvote = std::min<uint64_t>(h[mvk::IX_CTL_DG_NVOTE], nb), ndec = std::min<uint64_t>(h[mvk::IX_CTL_DG_NDEC], nb);
+  if (nvote * gmax > kMaxDecideWaves || ndec * gmax > kMaxDecideWaves)
+    return set_err(ctx, MV_E_INVALID_ARG, "decide: too many leader rows of one round for the records of its rounds");
+  HIPCHK(ctx, dg.sup.ensure(8 * (size_t)(nvote * gmax) + 8));
+  ds.sup = dg.sup.as<uint64_t>();
+  const auto& com = ctx->committee;
+  HIPCHK(ctx, mvk::launch_decide_rule(table_of(ctx, ix), d, nb, in, ds, nvote, ndec, dev.tab.stakes.as<uint64_t>(), com.size(),
+                                      com.quorum_threshold, d_out, d_stakes, ctl, s));
   return MV_OK;
 }
 
@@ -466,7 +608,10 @@ mv_status mv_index_clear(mv_ctx* ctx) {
   if (st != MV_OK) return st;
   Index& ix = dev->index;
   ix.pend.nb = ix.pend.ni = ix.pend.levels = 0;  // the store's records are slots of the table
+  ix.dag.nb = ix.dag.ni = 0;                     // ... and so are the DAG store's
   if (!ix.slots) return MV_OK;
+  if (ix.dag.on && ix.dag.map_slots)
+    HIPCHK(ctx, hipMemsetAsync(ix.dag.map.p, 0xff, 4 * (size_t)ix.dag.map_slots, dev->stream));
   HIPCHK(ctx, hipMemsetAsync(ix.tab.p, 0, kSlotBytes * ix.slots, dev->stream));
   HIPCHK(ctx, hipMemsetAsync(ix.ctl.p, 0, 8 * mvk::IX_CTL_WORDS, dev->stream));
   HIPCHK(ctx, hipStreamSynchronize(dev->stream));
@@ -767,6 +912,125 @@ mv_status mv_dev_connect_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, u
   *n_missing = ao.n_missing;
   *n_connected = total;
   return MV_OK;
+}
+
+mv_status mv_dag_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t includes) {
+  if (!ctx) return MV_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  Index& ix = dev->index;
+  Dag& dg = ix.dag;
+  hipStream_t s = dev->stream;
+  st = index_ctl(ctx, *dev, s);
+  if (st == MV_OK) st = dag_room(ctx, *dev, blocks > dg.nb ? blocks - dg.nb : 0, includes > dg.ni ? includes - dg.ni : 0, s);
+  if (st != MV_OK) return st;
+  if (!dg.on && ix.slots) {  // the map of the table in force (a later table brings its own)
+    HIPCHK(ctx, dg.map.ensure(4 * (size_t)ix.slots));
+    dg.map_slots = ix.slots;
+    HIPCHK(ctx, mvk::launch_dag_map(dag_view(dg), 0, ix.ctl.as<uint64_t>(), s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+  }
+  dg.on = true;
+  return MV_OK;
+}
+
+mv_status mv_dag_stats(mv_ctx* ctx, uint64_t* out) {
+  if (!ctx || !out) return set_err(ctx, MV_E_INVALID_ARG, "bad dag_stats args");
+  memset(out, 0, 4 * sizeof(uint64_t));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  Index& ix = dev->index;
+  if (!ix.dag.on || !ix.ctl.p) return MV_OK;
+  const uint64_t* w = nullptr;
+  st = read_ctl(ctx, *dev, dev->stream, &w);
+  out[0] = ix.dag.nb, out[1] = ix.dag.ni;
+  if (w && ix.dag.nb && w[mvk::IX_CTL_DG_NLO]) out[2] = ~w[mvk::IX_CTL_DG_NLO], out[3] = w[mvk::IX_CTL_DG_HI];
+  return st;
+}
+
+mv_status mv_dag_prune(mv_ctx* ctx, uint64_t round) {
+  if (!ctx) return MV_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  Index& ix = dev->index;
+  Dag& dg = ix.dag;
+  if (!dg.on) return set_err(ctx, MV_E_INVALID_ARG, "mv_dag_reserve first");
+  if (dg.nb == 0) return MV_OK;
+  hipStream_t s = dev->stream;
+  uint64_t* ctl = ix.ctl.as<uint64_t>();
+  DevBuf rec, inc;
+  if (rec.ensure(32 * (size_t)dg.cap_b) != hipSuccess || inc.ensure(8 * (size_t)dg.cap_i + 8) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(ctx, MV_E_ALLOC, "no device memory for the DAG store");
+  }
+  HIPCHK(ctx, dg.newbase.ensure(8 * (size_t)dg.nb));
+  HIPCHK(ctx, ix.wg.ensure(4 * 8 * mvk::index_groups(dg.nb)));
+  HIPCHK(ctx, hipMemsetAsync(ctl + mvk::IX_CTL_DG_NI, 0, 8 * (mvk::IX_CTL_DG_NB + 1 - mvk::IX_CTL_DG_NI), s));
+  HIPCHK(ctx, mvk::launch_dag_prune(dag_view(dg), dag_view(dg, rec, inc, dg.cap_b, dg.cap_i), dg.nb, round,
+                                    dg.newbase.as<uint64_t>(), ix.wg.as<uint64_t>(), ctl, s));
+  const uint64_t* h = nullptr;
+  st = read_ctl(ctx, *dev, s, &h);  // (synchronises: the old copy is read until here)
+  if (st != MV_OK) return st;
+  std::swap(dg.rec, rec);
+  std::swap(dg.inc, inc);
+  dg.nb = std::min<uint64_t>(h[mvk::IX_CTL_DG_NB], dg.nb);
+  dg.ni = std::min<uint64_t>(h[mvk::IX_CTL_DG_NI], dg.ni);
+  return MV_OK;
+}
+
+mv_status mv_decide_leaders(mv_ctx* ctx, const uint64_t* leaders, uint32_t n, uint64_t* out, uint64_t* stakes) {
+  if (!ctx || (n && (!leaders || !out))) return set_err(ctx, MV_E_INVALID_ARG, "bad decide args");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!committee_ready(ctx)) return set_err(ctx, MV_E_NO_COMMITTEE, "mv_set_committee first");
+  Device* dev;
+  mv_status st = index_dev(ctx, dev);
+  if (st != MV_OK) return st;
+  Dag& dg = dev->index.dag;
+  if (!dg.on) return set_err(ctx, MV_E_INVALID_ARG, "mv_dag_reserve first");
+  if (n == 0) return MV_OK;
+  hipStream_t s = dev->stream;
+  const size_t nn = n;
+  HIPCHK(ctx, dg.res.ensure(8 * 11 * nn));
+  uint64_t* d_out = dg.res.as<uint64_t>();
+  st = decide_run(ctx, *dev, leaders, n, d_out, stakes ? d_out + 8 * nn : nullptr, s);
+  if (st != MV_OK) {
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(out, d_out, 64 * nn, hipMemcpyDeviceToHost, s));
+  if (stakes) HIPCHK(ctx, hipMemcpyAsync(stakes, d_out + 8 * nn, 24 * nn, hipMemcpyDeviceToHost, s));
+  return read_ctl(ctx, *dev, s, nullptr);
+}
+
+mv_status mv_dev_decide_leaders(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_out,
+                                uint64_t* d_stakes, void* stream) {
+  if (!ctx || (n && (!d_leaders || !d_out))) return set_err(ctx, MV_E_INVALID_ARG, "bad decide args");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!committee_ready(ctx)) return set_err(ctx, MV_E_NO_COMMITTEE, "mv_set_committee first");
+  Device* dev = find_dev(ctx, device);
+  if (!dev || dev != &ctx->devs[0]) return set_err(ctx, MV_E_NO_DEVICE, "the index lives on the context's first device");
+  if (!dev->index.dag.on) return set_err(ctx, MV_E_INVALID_ARG, "mv_dag_reserve first");
+  if (n == 0) return MV_OK;
+  HIPCHK(ctx, hipSetDevice(dev->id));
+  reap_idle(ctx, *dev);
+  hipStream_t s = stream ? (hipStream_t)stream : dev->stream;
+  mv_status st = order_behind_ahead(ctx, *dev, s);
+  if (st != MV_OK) return st;
+  std::vector<uint64_t> leaders(2 * (size_t)n);  // sorted by round on the host
+  HIPCHK(ctx, hipMemcpyAsync(leaders.data(), d_leaders, 16 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  st = decide_run(ctx, *dev, leaders.data(), n, d_out, d_stakes, s);
+  if (st != MV_OK) {
+    (void)hipStreamSynchronize(s);
+    return st;
+  }
+  return read_ctl(ctx, *dev, s, nullptr);
 }
 
 }  // extern "C"

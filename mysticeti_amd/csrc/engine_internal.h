@@ -189,7 +189,20 @@ struct Device {
       int cur = 0;
       uint64_t nb = 0, ni = 0, cap_b = 0, cap_i = 0, levels = 0;
       DevBuf cand_slot, cand_dst, lvl, hit, newbase, rows;  // per candidate | per record scratch, the rows
+      DevBuf row_of;  // per record: the row it connected as (only with a DAG store)
     } pend;
+    // mv_dag_reserve / mv_decide_leaders: the DAG store (mvk::DagStore), made by mv_dag_reserve
+    // only -- rec holds slot | round | ibase | auth | kc for cap_b records, inc cap_i include
+    // slots, map a u32 per slot of the table (remade with it). Growing and pruning fill a fresh
+    // copy and swap.
+    struct Dag {
+      bool on = false;
+      DevBuf rec, inc, map;
+      uint64_t nb = 0, ni = 0, cap_b = 0, cap_i = 0, map_slots = 0;
+      // a connect call's row -> record scratch, a prune's new bases, and a decide call's sorted
+      // rows, per-row state, per-record lists, supports and results
+      DevBuf src, newbase, lead, state, lists, sup, res;
+    } dag;
   } index;
 
   // the resident online service (k_online) of this device, made on first use

@@ -715,7 +715,7 @@ __global__ void __launch_bounds__(1024) k_pb_scan(const uint64_t* __restrict__ w
 __global__ void __launch_bounds__(WG) k_pb_list(u64* __restrict__ slots, PendStore p, uint64_t nb,
                                                 const uint8_t* __restrict__ hit, const uint64_t* __restrict__ wgbase,
                                                 uint32_t* __restrict__ lvl, uint64_t level, uint64_t* __restrict__ out,
-                                                uint64_t cap, u64* __restrict__ ctl) {
+                                                uint64_t cap, u64* __restrict__ ctl, uint32_t* __restrict__ row_of) {
   const uint64_t b = (uint64_t)blockIdx.x * WG + threadIdx.x;
   const bool h = b < nb && hit[b];
   uint64_t tot;
@@ -723,6 +723,7 @@ __global__ void __launch_bounds__(WG) k_pb_list(u64* __restrict__ slots, PendSto
   if (h) {
     u64* slot = slots + SLOT_WORDS * p.slot[b];
     lvl[b] = (uint32_t)level + 1;
+    if (row_of) row_of[b] = (uint32_t)r;  // (with a DAG store: its record order is the row order)
     if (r < cap) {
 #pragma unroll
       for (int w = 0; w < 6; w++) out[8 * r + w] = slot[2 + w];  // (the key: written by an earlier launch)
@@ -802,6 +803,401 @@ __global__ void __launch_bounds__(WG) k_pb_reresolve(const u64* __restrict__ old
   }
   wave_max_to(ctl + mvk::IX_CTL_MAXPROBE, probe);
   wave_count_to(ctl + mvk::IX_CTL_ERR, fail);
+}
+
+// ---------------------------------------------------------------- the DAG store and the direct decision rule
+// mv_dag_reserve / mv_decide_leaders: the edges of the blocks mv_connect_blocks stored, and
+// BaseCommitter::try_direct_decide at wave length 3 over them (base_committer.rs:228-357; the
+// wording of every predicate is the header's). A record holds slots of the table, as PendStore
+// does; map[] gives the record of a slot. The memory model is the one at the top of this file:
+// lanes of one launch talk only through agent-scope atomic read-modify-writes on single words
+// (atomicOr into a bitmap, atomicAdd on a candidate count, atomicMax on a control word), no lane
+// waits for another, and what a kernel reads as plain data an earlier launch wrote. Inside one
+// wave, k_dg_cert collects a bitmap in LDS under wave-scope fences. Every slot number is checked
+// against the table size and every record number against the store's count before it is an
+// address; a number out of range counts into the error word (MV_E_HIP) and is not followed.
+//   k_dg_app_*   a connect call's rows join the store: records (and map[]), the scan of their
+//                include counts, the include slots a wave per row
+//   k_dg_keep_*  mv_dag_prune: k_pb_keep_*'s shape over "round >= floor"
+//   k_dg_pick_*  a lane per record: is it a voting (r + 1) or a decision (r + 2) record of a leader
+//                round, by binary search over the sorted distinct rounds; count / scan / list into
+//                vlist and dlist; a leader block adds itself to its rows' candidates
+//   k_dg_vote    a wave per (voting record, row of that round): any include of the authority, the
+//                first (authority, round) include in include order across batches of 64
+//   k_dg_cert    a wave per (decision record, row): the vote authors among its includes per candidate
+//   k_dg_decide  a wave per row: stakes of the bitmaps, the status and the row
+using mvk::DagStore;
+using mvk::DecideIn;
+using mvk::DecideState;
+constexpr uint32_t DG_NONE = mvk::DG_NONE;
+constexpr u64 DG_NO_SLOT = mvk::DG_NO_SLOT;
+constexpr uint32_t DG_MAX_AUTH = mvk::DG_MAX_AUTH;
+constexpr int DG_BM = mvk::DG_BM_WORDS;
+constexpr uint32_t DG_CAND = MV_DECIDE_MAX_LEADER_BLOCKS;
+
+__device__ inline void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ inline uint64_t shfl64(uint64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ inline uint64_t wave_sum64(uint64_t v) {
+  for (int d = 32; d; d >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
+    v += ((uint64_t)hi << 32) | lo;
+  }
+  return v;
+}
+// the stake of the authorities of a 16-word bitmap (every lane of the wave calls; lane j sums j, j + 64, ...)
+template <typename P>
+__device__ inline uint64_t bitmap_stake(P bm, const uint64_t* __restrict__ stakes, uint32_t n_auth) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t stake = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < DG_MAX_AUTH / 64; q++) {
+    const uint32_t a = lane + 64 * q;
+    if (a < n_auth && ((bm[a >> 5] >> (a & 31)) & 1u)) stake += stakes[a];
+  }
+  return wave_sum64(stake);
+}
+
+__global__ void __launch_bounds__(WG) k_dg_app_rows(const u64* __restrict__ slots, PendStore p, uint64_t nb,
+                                                    const uint32_t* __restrict__ lvl, const uint32_t* __restrict__ row_of,
+                                                    uint64_t rows, DagStore d, uint64_t nb0, uint64_t* __restrict__ src,
+                                                    u64* __restrict__ ctl) {
+  const uint64_t b = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool bad = false;
+  if (b < nb && lvl[b] != 0) {
+    const uint64_t r = row_of[b], s = p.slot[b], rec = nb0 + r;
+    bad = r >= rows || rec >= d.cap_b || s >= d.n_slots;
+    if (!bad) {
+      const u64* slot = slots + SLOT_WORDS * s;  // (the key: written by an earlier launch)
+      const u64 a = slot[2], rd = slot[3];
+      d.slot[rec] = s;
+      d.auth[rec] = a < DG_MAX_AUTH ? (uint32_t)a : DG_NONE;
+      d.round[rec] = rd;
+      d.kc[rec] = p.kc[b];
+      d.map[s] = (uint32_t)rec;
+      src[r] = b;
+      atomicMax(ctl + mvk::IX_CTL_DG_NLO, ~rd);
+      atomicMax(ctl + mvk::IX_CTL_DG_HI, rd);
+    }
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
+}
+// (src[r] is IX_NO_SRC for a row k_dg_app_rows refused: its record is not read)
+__device__ inline uint64_t app_kc(const DagStore& d, uint64_t nb0, uint64_t rows, const uint64_t* src, uint64_t r) {
+  return r < rows && src[r] != mvk::IX_NO_SRC ? d.kc[nb0 + r] : 0;
+}
+__global__ void __launch_bounds__(WG) k_dg_app_count(DagStore d, uint64_t nb0, uint64_t rows, const uint64_t* __restrict__ src,
+                                                     uint64_t* __restrict__ wgcount) {
+  const uint64_t r = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t tot;
+  (void)wg_excl(app_kc(d, nb0, rows, src, r), &tot);
+  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(WG) k_dg_app_list(DagStore d, uint64_t nb0, uint64_t ni0, uint64_t rows,
+                                                    const uint64_t* __restrict__ src, const uint64_t* __restrict__ wgbase) {
+  const uint64_t r = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t tot;
+  const uint64_t ib = ni0 + wgbase[blockIdx.x] + wg_excl(app_kc(d, nb0, rows, src, r), &tot);
+  if (r < rows && src[r] != mvk::IX_NO_SRC) d.ibase[nb0 + r] = ib;
+}
+__global__ void __launch_bounds__(WG) k_dg_app_inc(PendStore p, uint64_t nb, DagStore d, uint64_t nb0, uint64_t rows,
+                                                   const uint64_t* __restrict__ src, u64* __restrict__ ctl) {
+  const uint64_t r = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // a wave per row
+  if (r >= rows) return;
+  const uint64_t b = src[r];
+  bool bad = b >= nb;
+  if (!bad) {
+    const uint64_t from = p.ibase[b], to = d.ibase[nb0 + r];
+    const uint32_t kc = d.kc[nb0 + r];
+    bad = to > d.cap_i || kc > d.cap_i - to;
+    if (!bad)
+      for (uint32_t i = threadIdx.x & 63; i < kc; i += 64) d.inc[to + i] = p.inc[from + i];
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad && (threadIdx.x & 63) == 0);
+}
+
+__global__ void __launch_bounds__(WG) k_dg_map(DagStore d, uint64_t nb, u64* __restrict__ ctl) {
+  const uint64_t b = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool bad = false;
+  if (b < nb) {
+    const uint64_t s = d.slot[b];
+    bad = s >= d.n_slots;
+    if (!bad) d.map[s] = (uint32_t)b;
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
+}
+
+__global__ void __launch_bounds__(WG) k_dg_keep_count(DagStore d, uint64_t nb, uint64_t floor, uint64_t* __restrict__ wg_a,
+                                                      uint64_t* __restrict__ wg_b) {
+  const uint64_t b = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  const bool keep = b < nb && d.round[b] >= floor;
+  uint64_t tb, tk;
+  (void)wg_excl(keep, &tb);
+  (void)wg_excl(keep ? d.kc[b] : 0, &tk);
+  if (threadIdx.x == 0) {
+    wg_a[blockIdx.x] = tb;
+    wg_b[blockIdx.x] = tk;
+  }
+}
+__global__ void __launch_bounds__(WG) k_dg_keep_list(DagStore d, DagStore q, uint64_t nb, uint64_t floor,
+                                                     const uint64_t* __restrict__ base_a, const uint64_t* __restrict__ base_b,
+                                                     uint64_t* __restrict__ newbase, u64* __restrict__ ctl) {
+  const uint64_t b = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool keep = b < nb && d.round[b] >= floor;
+  const uint32_t kc = keep ? d.kc[b] : 0;
+  uint64_t tb, tk;
+  const uint64_t rb = base_a[blockIdx.x] + wg_excl(keep, &tb);
+  const uint64_t ib = base_b[blockIdx.x] + wg_excl(kc, &tk);
+  bool bad = false;
+  if (b < nb) {
+    const uint64_t s = keep ? d.slot[b] : 0;
+    bad = keep && (rb >= q.cap_b || ib > q.cap_i || kc > q.cap_i - ib || s >= q.n_slots);
+    keep = keep && !bad;
+    newbase[b] = keep ? ib : mvk::IX_NO_SRC;
+    if (keep) {
+      const uint64_t rd = d.round[b];
+      q.slot[rb] = s;
+      q.auth[rb] = d.auth[b];
+      q.round[rb] = rd;
+      q.ibase[rb] = ib;
+      q.kc[rb] = kc;
+      q.map[s] = (uint32_t)rb;
+      atomicMax(ctl + mvk::IX_CTL_DG_NLO, ~rd);
+      atomicMax(ctl + mvk::IX_CTL_DG_HI, rd);
+    }
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
+}
+__global__ void __launch_bounds__(WG) k_dg_keep_inc(DagStore d, DagStore q, uint64_t nb, const uint64_t* __restrict__ newbase) {
+  const uint64_t b = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // a wave per record
+  if (b >= nb || newbase[b] == mvk::IX_NO_SRC) return;
+  const uint64_t from = d.ibase[b], to = newbase[b];
+  const uint32_t kc = d.kc[b];
+  if (from > d.cap_i || kc > d.cap_i - from) return;  // (k_dg_keep_list checked the other side)
+  for (uint32_t i = threadIdx.x & 63; i < kc; i += 64) q.inc[to + i] = d.inc[from + i];
+}
+
+// *g = the place of `round` among the call's distinct leader rounds
+__device__ inline bool leader_group(const DecideIn& in, uint64_t round, uint64_t* g) {
+  uint64_t lo = 0, hi = in.ng;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (in.g_round[mid] < round) lo = mid + 1;
+    else hi = mid;
+  }
+  *g = lo;
+  return lo < in.ng && in.g_round[lo] == round;
+}
+__device__ inline void pick_roles(const DagStore& d, uint64_t nb, const DecideIn& in, uint64_t rec, bool* voting,
+                                  bool* decision) {
+  uint64_t g;
+  const uint64_t rd = rec < nb ? d.round[rec] : 0;
+  *voting = rec < nb && rd >= 1 && leader_group(in, rd - 1, &g);
+  *decision = rec < nb && rd >= 2 && leader_group(in, rd - 2, &g);
+}
+__global__ void __launch_bounds__(WG) k_dg_pick_count(DagStore d, uint64_t nb, DecideIn in, uint64_t* __restrict__ wg_a,
+                                                      uint64_t* __restrict__ wg_b) {
+  const uint64_t rec = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool v, c;
+  pick_roles(d, nb, in, rec, &v, &c);
+  uint64_t tv, tc;
+  (void)wg_excl(v, &tv);
+  (void)wg_excl(c, &tc);
+  if (threadIdx.x == 0) {
+    wg_a[blockIdx.x] = tv;
+    wg_b[blockIdx.x] = tc;
+  }
+}
+__global__ void __launch_bounds__(WG) k_dg_pick_list(DagStore d, uint64_t nb, DecideIn in, DecideState st,
+                                                     const uint64_t* __restrict__ base_a, const uint64_t* __restrict__ base_b) {
+  const uint64_t rec = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool v, c;
+  pick_roles(d, nb, in, rec, &v, &c);
+  uint64_t tv, tc;
+  const uint64_t pv = base_a[blockIdx.x] + wg_excl(v, &tv);
+  const uint64_t pc = base_b[blockIdx.x] + wg_excl(c, &tc);
+  if (rec >= nb) return;
+  st.vpos[rec] = v && pv < nb ? (uint32_t)pv : DG_NONE;
+  if (v && pv < nb) st.vlist[pv] = (uint32_t)rec;
+  if (c && pc < nb) st.dlist[pc] = (uint32_t)rec;
+  uint64_t g;
+  if (!leader_group(in, d.round[rec], &g)) return;
+  // a leader block of every row (authority, round) that names it; bounded by the rows of the round
+  const uint64_t a = d.auth[rec], hi = in.g_start[g + 1] < in.n ? in.g_start[g + 1] : in.n;
+  for (uint64_t k = in.g_start[g]; k < hi; k++) {
+    if (in.l_auth[k] != a) continue;
+    const uint32_t at = atomicAdd(st.cand_n + k, 1u);
+    if (at < DG_CAND) st.cand_slot[DG_CAND * k + at] = d.slot[rec];
+  }
+}
+
+// which (record of a list, row) a wave works on; false: none
+__device__ inline bool wave_task(const DagStore& d, uint64_t nb, const DecideIn& in, const uint32_t* __restrict__ list,
+                                 uint64_t n_list, uint64_t back, uint64_t* at, uint64_t* j, uint64_t* rec, uint64_t* k,
+                                 bool* bad) {
+  const uint64_t w = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // the same for the whole wave
+  *at = w / in.gmax, *j = w % in.gmax;
+  if (*at >= n_list) return false;
+  *rec = list[*at];
+  if (*rec >= nb) {
+    *bad = true;
+    return false;
+  }
+  const uint64_t rd = d.round[*rec];
+  uint64_t g;
+  if (rd < back || !leader_group(in, rd - back, &g)) return false;
+  *k = in.g_start[g] + *j;
+  return *k < in.g_start[g + 1] && *k < in.n;
+}
+
+__global__ void __launch_bounds__(WG) k_dg_vote(const u64* __restrict__ slots, DagStore d, uint64_t nb, DecideIn in,
+                                                DecideState st, uint64_t nvote, u64* __restrict__ ctl) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t vi, j, rec, k;
+  bool bad = false;
+  if (wave_task(d, nb, in, st.vlist, nvote, 1, &vi, &j, &rec, &k, &bad)) {
+    const uint64_t a = in.l_auth[k], r = in.l_round[k];
+    const uint64_t base = d.ibase[rec];
+    const uint32_t kc = d.kc[rec];
+    bad = base > d.cap_i || kc > d.cap_i - base;
+    if (!bad) {
+      bool any = false;
+      u64 sup = DG_NO_SLOT;
+      for (uint32_t q0 = 0; q0 < kc; q0 += 64) {  // bounded by the include count; the wave stays together
+        const uint32_t q = q0 + lane;
+        u64 s = DG_NO_SLOT;
+        bool has_a = false, match = false;
+        if (q < kc) {
+          s = d.inc[base + q];
+          if (s < d.n_slots) {
+            has_a = slots[SLOT_WORDS * s + 2] == a;  // the authority only (base_committer.rs:234-237)
+            match = has_a && slots[SLOT_WORDS * s + 3] == r;
+          } else {
+            bad = true;
+          }
+        }
+        any = any || __ballot(has_a) != 0;
+        const u64 m = __ballot(match);
+        if (m && sup == DG_NO_SLOT) sup = shfl64(s, __ffsll((long long)m) - 1);  // the first in include order
+      }
+      const uint32_t author = d.auth[rec];
+      if (lane == 0) {
+        st.sup[vi * in.gmax + j] = sup;
+        if (author < DG_MAX_AUTH) {
+          const uint32_t bit = 1u << (author & 31);
+          if (!any) atomicOr(st.blame + DG_BM * k + (author >> 5), bit);
+          const uint32_t found = st.cand_n[k], cn = found < DG_CAND ? found : DG_CAND;
+          for (uint32_t c = 0; c < cn; c++)
+            if (sup != DG_NO_SLOT && st.cand_slot[DG_CAND * k + c] == sup)
+              atomicOr(st.vote + DG_BM * (DG_CAND * k + c) + (author >> 5), bit);
+        }
+      }
+    }
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
+}
+
+__global__ void __launch_bounds__(WG) k_dg_cert(DagStore d, uint64_t nb, DecideIn in, DecideState st, uint64_t nvote,
+                                                uint64_t ndec, const uint64_t* __restrict__ stakes, uint32_t n_auth,
+                                                uint64_t quorum_thr, u64* __restrict__ ctl) {
+  __shared__ uint32_t bms[WG / 64][DG_CAND][DG_BM];
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t(*bm)[DG_BM] = bms[threadIdx.x / 64];
+  uint64_t di, j, rec, k;
+  bool bad = false;
+  if (wave_task(d, nb, in, st.dlist, ndec, 2, &di, &j, &rec, &k, &bad)) {
+    const uint32_t found = st.cand_n[k], cn = found < DG_CAND ? found : DG_CAND;
+    const uint32_t author = d.auth[rec];
+    const uint64_t base = d.ibase[rec], vround = d.round[rec] - 1;
+    const uint32_t kc = d.kc[rec];
+    bad = base > d.cap_i || kc > d.cap_i - base;
+    if (!bad && cn && author < n_auth && author < DG_MAX_AUTH) {
+      for (uint32_t i = lane; i < DG_CAND * DG_BM; i += 64) (&bm[0][0])[i] = 0;
+      wave_sync();
+      for (uint32_t q0 = 0; q0 < kc; q0 += 64) {
+        const uint32_t q = q0 + lane;
+        if (q >= kc) continue;
+        const u64 s = d.inc[base + q];
+        if (s >= d.n_slots) {
+          bad = true;
+          continue;
+        }
+        const uint32_t v = d.map[s];  // an include without a record (seeded, pruned) votes for nothing
+        if (v == DG_NONE) continue;
+        if (v >= nb) {
+          bad = true;
+          continue;
+        }
+        const uint32_t va = d.auth[v], vp = st.vpos[v];
+        if (d.round[v] != vround || va >= n_auth || va >= DG_MAX_AUTH || vp >= nvote) continue;
+        const u64 sup = st.sup[(uint64_t)vp * in.gmax + j];  // (k_dg_vote's, an earlier launch)
+        if (sup == DG_NO_SLOT) continue;
+        for (uint32_t c = 0; c < cn; c++)
+          if (st.cand_slot[DG_CAND * k + c] == sup) atomicOr(&bm[c][va >> 5], 1u << (va & 31));
+      }
+      wave_sync();
+      for (uint32_t c = 0; c < cn; c++) {
+        const uint64_t stake = bitmap_stake(bm[c], stakes, n_auth);
+        if (lane == 0 && stake > quorum_thr)
+          atomicOr(st.cert + DG_BM * (DG_CAND * k + c) + (author >> 5), 1u << (author & 31));
+      }
+    }
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
+}
+
+__global__ void __launch_bounds__(WG) k_dg_decide(const u64* __restrict__ slots, uint64_t n_slots, DecideIn in, DecideState st,
+                                                  const uint64_t* __restrict__ stakes, uint32_t n_auth, uint64_t quorum_thr,
+                                                  uint64_t* __restrict__ out, uint64_t* __restrict__ stakes_out,
+                                                  u64* __restrict__ ctl) {
+  const uint64_t k = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // a wave per row
+  const uint32_t lane = threadIdx.x & 63;
+  if (k >= in.n) return;
+  const uint64_t a = in.l_auth[k], r = in.l_round[k], row = in.l_row[k];
+  if (row >= in.n) return;
+  uint64_t w[8] = {a, r, 0, 0, 0, 0, MV_LEADER_UNDECIDED, 0}, sk[3] = {0, 0, 0};
+  bool bad = false;
+  if (a < n_auth) {
+    const uint32_t found = st.cand_n[k], cn = found < DG_CAND ? found : DG_CAND;
+    const uint64_t blame = bitmap_stake(st.blame + DG_BM * k, stakes, n_auth);
+    uint64_t best_v = 0, best_c = 0, com_v = 0, com_c = 0;
+    u64 com_slot = DG_NO_SLOT;
+    uint32_t enough = 0;
+    for (uint32_t c = 0; c < cn; c++) {
+      const uint64_t v = bitmap_stake(st.vote + DG_BM * (DG_CAND * k + c), stakes, n_auth);
+      const uint64_t ce = bitmap_stake(st.cert + DG_BM * (DG_CAND * k + c), stakes, n_auth);
+      if (v > best_v || (v == best_v && ce > best_c)) best_v = v, best_c = ce;
+      if (ce > quorum_thr) enough++, com_v = v, com_c = ce, com_slot = st.cand_slot[DG_CAND * k + c];
+    }
+    const u64 nlo = ctl[mvk::IX_CTL_DG_NLO];  // max of ~round over the records, 0 without any
+    uint64_t status = MV_LEADER_UNDECIDED;
+    if (nlo == 0 || r < ~nlo) status = MV_LEADER_UNDECIDED;  // below the lowest retained round
+    else if (blame > quorum_thr) status = MV_LEADER_SKIP;
+    else if (found > DG_CAND) status = MV_LEADER_OVERFLOW;
+    else if (enough == 1) status = MV_LEADER_COMMIT;
+    else if (enough > 1) status = MV_LEADER_CONFLICT;
+    if (status == MV_LEADER_COMMIT) {
+      bad = com_slot >= n_slots;
+      if (bad) status = MV_LEADER_UNDECIDED;
+      else
+        for (int i = 0; i < 6; i++) w[i] = slots[SLOT_WORDS * com_slot + 2 + i];
+    }
+    w[6] = status, w[7] = found;
+    sk[0] = blame;
+    if (found <= DG_CAND) sk[1] = enough == 1 ? com_v : best_v, sk[2] = enough == 1 ? com_c : best_c;
+  }
+  if (lane == 0) {
+    for (int i = 0; i < 8; i++) out[8 * row + i] = w[i];
+    if (stakes_out)
+      for (int i = 0; i < 3; i++) stakes_out[3 * row + i] = sk[i];
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad && lane == 0);
 }
 
 static inline uint32_t grid_of(uint64_t items) { return (uint32_t)((items + WG - 1) / WG); }
@@ -934,14 +1330,14 @@ hipError_t launch_pend_append(const AcceptArrays& a, uint64_t ncand, uint64_t ni
 
 hipError_t launch_pend_level(const IndexTable& t, const PendStore& p, uint64_t nb, uint32_t* lvl, uint8_t* hit,
                              uint64_t level, uint64_t* wg, uint64_t* out, uint64_t cap, uint64_t* ctl, int lv_word,
-                             hipStream_t s) {
+                             uint32_t* row_of, hipStream_t s) {
   if (nb == 0) return hipSuccess;
   const uint64_t nwg = index_groups(nb);
   const dim3 g(grid_of(nb)), b(WG);
   hipLaunchKernelGGL(k_pb_check, dim3(grid_of(64 * nb)), b, 0, s, (const u64*)t.slots, p, nb, lvl, hit);
   hipLaunchKernelGGL(k_pb_count, g, b, 0, s, hit, nb, wg);
   hipLaunchKernelGGL(k_pb_scan, dim3(1), dim3(1024), 0, s, wg, nwg, wg + nwg, ctl + IX_CTL_PB_ROWS, ctl + lv_word);
-  hipLaunchKernelGGL(k_pb_list, g, b, 0, s, (u64*)t.slots, p, nb, hit, wg + nwg, lvl, level, out, cap, (u64*)ctl);
+  hipLaunchKernelGGL(k_pb_list, g, b, 0, s, (u64*)t.slots, p, nb, hit, wg + nwg, lvl, level, out, cap, (u64*)ctl, row_of);
   return hipGetLastError();
 }
 
@@ -963,6 +1359,80 @@ hipError_t launch_pend_reresolve(const uint64_t* old_slots, const IndexTable& t,
                                  uint64_t* ctl, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_pb_reresolve, dim3(grid_of(n)), dim3(WG), 0, s, (const u64*)old_slots, t, slotidx, n, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_dag_append(const IndexTable& t, const PendStore& p, uint64_t nb, const uint32_t* lvl,
+                             const uint32_t* row_of, uint64_t rows, const DagStore& d, uint64_t nb0, uint64_t ni0,
+                             uint64_t* src, uint64_t* wg, uint64_t* ctl, hipStream_t s) {
+  if (rows == 0 || nb == 0) return hipSuccess;
+  const uint64_t nwg = index_groups(rows);
+  const dim3 gr(grid_of(rows)), b(WG);
+  hipError_t e = hipMemsetAsync(src, 0xff, 8 * rows, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_dg_app_rows, dim3(grid_of(nb)), b, 0, s, (const u64*)t.slots, p, nb, lvl, row_of, rows, d, nb0, src,
+                     (u64*)ctl);
+  hipLaunchKernelGGL(k_dg_app_count, gr, b, 0, s, d, nb0, rows, src, wg);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg, nwg, wg + nwg, ctl + IX_CTL_DG_NI);
+  hipLaunchKernelGGL(k_dg_app_list, gr, b, 0, s, d, nb0, ni0, rows, src, wg + nwg);
+  hipLaunchKernelGGL(k_dg_app_inc, dim3(grid_of(64 * rows)), b, 0, s, p, nb, d, nb0, rows, src, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_dag_map(const DagStore& d, uint64_t nb, uint64_t* ctl, hipStream_t s) {
+  if (d.n_slots == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(d.map, 0xff, 4 * d.n_slots, s);
+  if (e != hipSuccess || nb == 0) return e;
+  hipLaunchKernelGGL(k_dg_map, dim3(grid_of(nb)), dim3(WG), 0, s, d, nb, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_dag_prune(const DagStore& d, const DagStore& q, uint64_t nb, uint64_t floor, uint64_t* newbase,
+                            uint64_t* wg, uint64_t* ctl, hipStream_t s) {
+  if (nb == 0) return hipSuccess;
+  const uint64_t nwg = index_groups(nb);
+  uint64_t *wg_a = wg, *wg_b = wg + nwg, *base_a = wg + 2 * nwg, *base_b = wg + 3 * nwg;
+  const dim3 g(grid_of(nb)), b(WG);
+  hipError_t e = hipMemsetAsync(q.map, 0xff, 4 * q.n_slots, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_dg_keep_count, g, b, 0, s, d, nb, floor, wg_a, wg_b);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg_a, nwg, base_a, ctl + IX_CTL_DG_NB);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg_b, nwg, base_b, ctl + IX_CTL_DG_NI);
+  hipLaunchKernelGGL(k_dg_keep_list, g, b, 0, s, d, q, nb, floor, base_a, base_b, newbase, (u64*)ctl);
+  hipLaunchKernelGGL(k_dg_keep_inc, dim3(grid_of(64 * nb)), b, 0, s, d, q, nb, newbase);
+  return hipGetLastError();
+}
+
+hipError_t launch_decide_pick(const DagStore& d, uint64_t nb, const DecideIn& in, const DecideState& st, uint64_t* wg,
+                              uint64_t* ctl, hipStream_t s) {
+  if (nb == 0) return hipSuccess;
+  const uint64_t nwg = index_groups(nb);
+  uint64_t *wg_a = wg, *wg_b = wg + nwg, *base_a = wg + 2 * nwg, *base_b = wg + 3 * nwg;
+  const dim3 g(grid_of(nb)), b(WG);
+  hipLaunchKernelGGL(k_dg_pick_count, g, b, 0, s, d, nb, in, wg_a, wg_b);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg_a, nwg, base_a, ctl + IX_CTL_DG_NVOTE);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg_b, nwg, base_b, ctl + IX_CTL_DG_NDEC);
+  hipLaunchKernelGGL(k_dg_pick_list, g, b, 0, s, d, nb, in, st, base_a, base_b);
+  return hipGetLastError();
+}
+
+hipError_t launch_decide_rule(const IndexTable& t, const DagStore& d, uint64_t nb, const DecideIn& in,
+                              const DecideState& st, uint64_t nvote, uint64_t ndec, const uint64_t* stakes,
+                              uint32_t n_auth, uint64_t quorum_thr, uint64_t* out, uint64_t* stakes_out, uint64_t* ctl,
+                              hipStream_t s) {
+  if (n_auth > DG_MAX_AUTH) return hipErrorInvalidValue;
+  const dim3 b(WG);
+  if (nvote) {
+    hipError_t e = hipMemsetAsync(st.sup, 0xff, 8 * nvote * in.gmax, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_dg_vote, dim3(grid_of(64 * nvote * in.gmax)), b, 0, s, (const u64*)t.slots, d, nb, in, st, nvote,
+                       (u64*)ctl);
+  }
+  if (ndec && nvote)
+    hipLaunchKernelGGL(k_dg_cert, dim3(grid_of(64 * ndec * in.gmax)), b, 0, s, d, nb, in, st, nvote, ndec, stakes, n_auth,
+                       quorum_thr, (u64*)ctl);
+  hipLaunchKernelGGL(k_dg_decide, dim3(grid_of(64 * in.n)), b, 0, s, (const u64*)t.slots, d.n_slots, in, st, stakes, n_auth,
+                     quorum_thr, out, stakes_out, (u64*)ctl);
   return hipGetLastError();
 }
 

@@ -449,7 +449,13 @@ constexpr uint64_t IX_MAX_ITEMS = 0xfffffffeull;  // items of one insert (the ow
 constexpr int IX_CTL_HAVE = 0, IX_CTL_WANTED = 1, IX_CTL_MAXPROBE = 2, IX_CTL_RETRY = 3, IX_CTL_ERR = 4,
               IX_CTL_NVER = 5, IX_CTL_NHEADS = 6, IX_CTL_NCAND = 7, IX_CTL_NINC = 8, IX_CTL_NMISS = 9,
               IX_CTL_NWANTED = 10, IX_CTL_STORED = 11, IX_CTL_PB_NB = 12, IX_CTL_PB_NI = 13, IX_CTL_PB_ROWS = 14,
-              IX_CTL_LV0 = 16, IX_CTL_LEVELS = 16, IX_CTL_WORDS = IX_CTL_LV0 + IX_CTL_LEVELS;
+              IX_CTL_LV0 = 16, IX_CTL_LEVELS = 16, IX_CTL_PB_END = IX_CTL_LV0 + IX_CTL_LEVELS,
+              // the DAG store's words: includes appended by the connect call that is running (or kept by
+              // a prune), max of ~round and of round over its records (0: no record), and the voting
+              // and decision records a decide call picked
+              IX_CTL_DG_NI = IX_CTL_PB_END, IX_CTL_DG_NLO = IX_CTL_DG_NI + 1, IX_CTL_DG_HI = IX_CTL_DG_NI + 2,
+              IX_CTL_DG_NVOTE = IX_CTL_DG_NI + 3, IX_CTL_DG_NDEC = IX_CTL_DG_NI + 4, IX_CTL_DG_NB = IX_CTL_DG_NI + 5,
+              IX_CTL_WORDS = IX_CTL_DG_NI + 8;
 uint64_t index_groups(uint64_t n);  // workgroups of the per-item kernels: wgcount / wgbase hold one word each
 hipError_t launch_index_scan(const uint64_t* wgcount, uint64_t nwg, uint64_t* wgbase, uint64_t* total, hipStream_t s);
 // one insert round (k_ix_claim, k_ix_fill, k_ix_settle) of n items towards `state`; item: n words
@@ -519,10 +525,11 @@ hipError_t launch_pend_append(const AcceptArrays& a, uint64_t ncand, uint64_t ni
                               uint64_t* wg /* 4 x index_groups(ncand) */, uint64_t* ctl, hipStream_t s);
 // One level of the sweep over the nb records: check (a wave per record), count, scan, list + raise.
 // lvl[b]: 0, or 1 + the level that connected b. Rows go to out (cap rows of 8 words) from row
-// ctl[IX_CTL_PB_ROWS] on; ctl[lv_word] = the rows of this level.
+// ctl[IX_CTL_PB_ROWS] on; ctl[lv_word] = the rows of this level. row_of (may be null; per record):
+// the row a record connected as, whatever the cap -- the DAG store's record order.
 hipError_t launch_pend_level(const IndexTable& t, const PendStore& p, uint64_t nb, uint32_t* lvl, uint8_t* hit,
                              uint64_t level, uint64_t* wg /* 2 x index_groups(nb) */, uint64_t* out, uint64_t cap,
-                             uint64_t* ctl, int lv_word, hipStream_t s);
+                             uint64_t* ctl, int lv_word, uint32_t* row_of, hipStream_t s);
 // Stable compaction of p's records that are not STORED into q; those of the running call become
 // MV_ACC_SUSPENDED in state (n_state entries, may be null). ctl[IX_CTL_PB_NB], ctl[IX_CTL_PB_NI] = what q holds.
 hipError_t launch_pend_compact(const IndexTable& t, const PendStore& p, const PendStore& q, uint64_t nb, uint64_t* newbase,
@@ -530,4 +537,65 @@ hipError_t launch_pend_compact(const IndexTable& t, const PendStore& p, const Pe
 // after launch_index_rebuild: n slot numbers of the old table become those of the same keys in t
 hipError_t launch_pend_reresolve(const uint64_t* old_slots, const IndexTable& t, uint64_t* slotidx, uint64_t n,
                                  uint64_t* ctl, hipStream_t s);
+
+// The DAG store (mv_dag_reserve, mv_decide_leaders; kernels and memory model: index.hip): one
+// record per block that mv_connect_blocks stored, in connected-row order, with its includes as
+// slots of the table. map: per slot of the table the record of its reference, DG_NONE without one.
+struct DagStore {
+  uint64_t* slot;   // per record: the slot of its own reference
+  uint64_t* round;  // its round and
+  uint32_t* auth;   // its authority, as the slot's key has them
+  uint64_t* ibase;  // the number of its first include in inc
+  uint32_t* kc;     // its include count
+  uint64_t* inc;    // per include: its slot
+  uint32_t* map;    // per slot of the table: its record
+  uint64_t cap_b, cap_i, n_slots;  // what the arrays hold: every index is checked against them
+};
+constexpr uint32_t DG_NONE = 0xffffffffu;
+constexpr uint64_t DG_NO_SLOT = ~0ull;
+constexpr uint32_t DG_MAX_AUTH = 512;  // the bitmaps are 16 words (the walk's threshold-clock bitmap)
+constexpr int DG_BM_WORDS = DG_MAX_AUTH / 32;
+// The rows of a connect call (records of p with lvl != 0, row row_of[b]) join d behind its nb0
+// records and ni0 includes: the records, the scan of their include counts (ctl[IX_CTL_DG_NI] = the
+// includes), the include slots a wave per row. src: rows words of scratch; wg: 2 x index_groups(rows).
+hipError_t launch_dag_append(const IndexTable& t, const PendStore& p, uint64_t nb, const uint32_t* lvl,
+                             const uint32_t* row_of, uint64_t rows, const DagStore& d, uint64_t nb0, uint64_t ni0,
+                             uint64_t* src, uint64_t* wg, uint64_t* ctl, hipStream_t s);
+// map[] = DG_NONE, then map[slot of record b] = b for d's nb records
+hipError_t launch_dag_map(const DagStore& d, uint64_t nb, uint64_t* ctl, hipStream_t s);
+// Stable compaction of d's records of round >= floor into q (whose map is rebuilt);
+// ctl[IX_CTL_DG_NB], ctl[IX_CTL_DG_NI] = what q holds, ctl[IX_CTL_DG_NLO / _HI] its rounds.
+hipError_t launch_dag_prune(const DagStore& d, const DagStore& q, uint64_t nb, uint64_t floor, uint64_t* newbase,
+                            uint64_t* wg /* 4 x index_groups(nb) */, uint64_t* ctl, hipStream_t s);
+
+// One decide call over n leader rows sorted by round: the distinct rounds (ng of them), where each
+// round's rows start (ng + 1 words), and per sorted row its authority, round and place in the
+// caller's arrays. gmax: the most rows of one round.
+struct DecideIn {
+  const uint64_t* g_round;
+  const uint64_t* g_start;
+  const uint64_t* l_auth;
+  const uint64_t* l_round;
+  const uint64_t* l_row;
+  uint64_t ng, n, gmax;
+};
+struct DecideState {  // zeroed by the caller except vpos / vlist / dlist / sup
+  uint32_t* cand_n;     // per row: leader blocks found
+  uint64_t* cand_slot;  // per row x 8: their slots
+  uint32_t* blame;      // per row x 16: authors of voting blocks without an include of the authority
+  uint32_t* vote;       // per row x 8 x 16: authors of voting blocks that vote for the block
+  uint32_t* cert;       // per row x 8 x 16: authors of its certificates
+  uint32_t* vpos;       // per record: its place in vlist, DG_NONE outside it
+  uint32_t* vlist;      // the voting records, the decision records
+  uint32_t* dlist;
+  uint64_t* sup;        // per (place in vlist, row of that round): the supported slot, DG_NO_SLOT for none
+};
+// k_dg_pick: vpos, vlist, dlist, the candidates; ctl[IX_CTL_DG_NVOTE], ctl[IX_CTL_DG_NDEC]
+hipError_t launch_decide_pick(const DagStore& d, uint64_t nb, const DecideIn& in, const DecideState& st,
+                              uint64_t* wg /* 4 x index_groups(nb) */, uint64_t* ctl, hipStream_t s);
+// k_dg_vote, k_dg_cert, k_dg_decide: out (n x 8) and stakes_out (n x 3, may be null) in the caller's row order
+hipError_t launch_decide_rule(const IndexTable& t, const DagStore& d, uint64_t nb, const DecideIn& in,
+                              const DecideState& st, uint64_t nvote, uint64_t ndec, const uint64_t* stakes,
+                              uint32_t n_auth, uint64_t quorum_thr, uint64_t* out, uint64_t* stakes_out, uint64_t* ctl,
+                              hipStream_t s);
 }  // namespace mvk

@@ -37,6 +37,13 @@ pub const MV_ACC_DUP: u8 = 3;
 pub const MV_ACC_DROPPED: u8 = 4;
 pub const MV_ACC_SUSPENDED: u8 = 5;
 
+pub const MV_LEADER_UNDECIDED: u64 = 0;
+pub const MV_LEADER_COMMIT: u64 = 1;
+pub const MV_LEADER_SKIP: u64 = 2;
+pub const MV_LEADER_CONFLICT: u64 = 3;
+pub const MV_LEADER_OVERFLOW: u64 = 4;
+pub const MV_DECIDE_MAX_LEADER_BLOCKS: u64 = 8;
+
 pub const MV_SIG_OK: u8 = 0;
 pub const MV_SIG_INVALID: u8 = 1;
 pub const MV_SIG_MALFORMED_KEY: u8 = 2;
@@ -142,6 +149,12 @@ extern "C" {
                                  cap_connected: u64, n_connected: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_pending_reserve(ctx: *mut mv_ctx, blocks: u64, includes: u64) -> i32;
     pub fn mv_pending_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
+    pub fn mv_dag_reserve(ctx: *mut mv_ctx, blocks: u64, includes: u64) -> i32;
+    pub fn mv_dag_prune(ctx: *mut mv_ctx, round: u64) -> i32;
+    pub fn mv_dag_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
+    pub fn mv_decide_leaders(ctx: *mut mv_ctx, leaders: *const u64, n: u32, out: *mut u64, stakes: *mut u64) -> i32;
+    pub fn mv_dev_decide_leaders(ctx: *mut mv_ctx, device: i32, d_leaders: *const u64, n: u32, d_out: *mut u64,
+                                 d_stakes: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_dev_index_insert(ctx: *mut mv_ctx, device: i32, d_words: *const u64, stride_words: u64, n: u64,
                                state: u32, stream: *mut c_void) -> i32;
     pub fn mv_dev_verify_frames(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,

@@ -277,6 +277,44 @@ impl GpuVerifier {
     }
 }
 
+impl GpuVerifier {
+    /// Keeps the edges of what `connect_blocks` connects in device memory (mv_dag_reserve): the
+    /// store `decide_leaders` reads. Call once, before the first connect call.
+    pub fn dag_reserve(&self, blocks: u64, includes: u64) -> eyre::Result<()> {
+        let rc = unsafe { sys::mv_dag_reserve(self.ctx, blocks, includes) };
+        ensure!(rc == sys::MV_OK, "mv_dag_reserve: {}", self.last_error());
+        Ok(())
+    }
+
+    /// BlockStore::cleanup for the DAG store (mv_dag_prune): drops the records below `round`.
+    pub fn dag_prune(&self, round: u64) -> eyre::Result<()> {
+        let rc = unsafe { sys::mv_dag_prune(self.ctx, round) };
+        ensure!(rc == sys::MV_OK, "mv_dag_prune: {}", self.last_error());
+        Ok(())
+    }
+
+    /// BaseCommitter::try_direct_decide (consensus/base_committer.rs:323-357) for every elected
+    /// leader (authority, round) of `leaders`, on the GPU (mv_decide_leaders). The caller elects
+    /// the leaders, and runs try_indirect_decide, the longest-decided-prefix rule and the
+    /// linearizer on the rows; an MV_LEADER_OVERFLOW row it decides itself.
+    pub fn decide_leaders(&self, leaders: &[(u64, u64)]) -> eyre::Result<Decided> {
+        let n = leaders.len();
+        let flat: Vec<u64> = leaders.iter().flat_map(|&(a, r)| [a, r]).collect();
+        let mut d = Decided { rows: vec![0u64; 8 * n], stakes: vec![0u64; 3 * n] };
+        let rc = unsafe {
+            sys::mv_decide_leaders(self.ctx, flat.as_ptr(), n as u32, d.rows.as_mut_ptr(), d.stakes.as_mut_ptr())
+        };
+        ensure!(rc == sys::MV_OK, "mv_decide_leaders: {}", self.last_error());
+        Ok(d)
+    }
+}
+
+/// Result of `GpuVerifier::decide_leaders` (layout: include/mysti_verify.h, mv_decide_leaders).
+pub struct Decided {
+    pub rows: Vec<u64>,   // eight words per leader: the committed reference, MV_LEADER_*, leader blocks found
+    pub stakes: Vec<u64>, // three per leader: blame, vote and certificate stake
+}
+
 /// Result of `GpuVerifier::connect_blocks` (layout: include/mysti_verify.h, mv_connect_blocks).
 pub struct Connected {
     pub accepted: Accepted,  // blk_state: MV_ACC_SUSPENDED for the blocks that wait in the store
