@@ -461,14 +461,46 @@ __global__ void __launch_bounds__(256) k_part_top(const uint32_t* __restrict__ p
 // arbitrary, which no later stage depends on (the fine sort orders by key, and a bucket's sum
 // does not depend on the order of its points).
 // (scal, n: the signatures [base, base + n) of a batch of nall; point refs are batch-wide)
+//
+// The entry between the two passes (tmp) has two forms, one kernel template over its type E.
+// What the fine sort needs of an entry is the key's low BV_FINE_BITS bits (its bin) and the point
+// reference ref = pt << 1 | sign; the partition key >> BV_FINE_BITS is where the entry lies.
+//   uint32_t (narrow)   bin << 24 | ref, for batches with 2 * nall <= 2^23 (pt < 2 * nall, so
+//                       ref < 2^24): half the bytes stored and read back, half the LDS staging
+//   unsigned long long  (g * BV_NKG + key) << 32 | ref, any batch size (and MV_SORT_WIDE = 1)
+template <class E>
+struct PartEntry;
+template <>
+struct PartEntry<uint32_t> {
+  static constexpr bool narrow = true;
+  static constexpr uint32_t REF_BITS = 32 - BV_FINE_BITS;
+  static MV_DEV uint32_t make(uint32_t gkey, uint32_t ref) { return gkey << REF_BITS | ref; }  // the low key bits stay
+  static MV_DEV uint32_t bin(uint32_t e) { return e >> REF_BITS; }
+  static MV_DEV uint32_t ref(uint32_t e) { return e & ((1u << REF_BITS) - 1); }
+};
+template <>
+struct PartEntry<unsigned long long> {
+  static constexpr bool narrow = false;
+  static MV_DEV unsigned long long make(uint32_t gkey, uint32_t ref) { return (unsigned long long)gkey << 32 | ref; }
+  static MV_DEV uint32_t bin(unsigned long long e) { return (uint32_t)(e >> 32) & ((1u << BV_FINE_BITS) - 1); }
+  static MV_DEV uint32_t ref(unsigned long long e) { return (uint32_t)e; }
+};
+// the largest batch whose point references fit the narrow entry
+constexpr uint32_t BV_NARROW_MAX_N = 1u << (PartEntry<uint32_t>::REF_BITS - 2);
+
 constexpr uint32_t BV_PPW = BV_NB >> BV_FINE_BITS;  // partitions per window (128)
+template <class E>
 __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __restrict__ scal, uint32_t n,
                                                                  const uint32_t* __restrict__ pcount,
                                                                  const uint32_t* __restrict__ poff,
                                                                  const uint32_t* __restrict__ pstart, BvGroups G,
                                                                  uint32_t skipA, uint32_t nall, uint32_t base,
-                                                                 unsigned long long* __restrict__ tmp) {
-  __shared__ unsigned long long buf[2 * PART_CHUNK];  // one window's entries (<= 2 per signature)
+                                                                 E* __restrict__ tmp) {
+  using PE = PartEntry<E>;
+  __shared__ E buf[2 * PART_CHUNK];  // one window's entries (<= 2 per signature)
+  // narrow: the window-local partition of every slot of buf (the entry no longer holds it)
+  __shared__ uint8_t bpl[PE::narrow ? 2 * PART_CHUNK : 1];
+  static_assert(BV_PPW <= 256, "a slot's partition fits a byte");
   __shared__ uint32_t lofs[BV_PPW + 1], gpos[BV_PPW], rank[BV_PPW];
   const uint32_t gid = blockIdx.x * PART_CHUNK + threadIdx.x;
   const bool live = gid < n;
@@ -518,16 +550,22 @@ __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __
     __syncthreads();
     auto place = [&](int d, uint32_t pt) {
       const uint32_t key = bv_key(w, d), pl = (key >> BV_FINE_BITS) & (BV_PPW - 1);
-      const uint32_t r = atomicAdd(&rank[pl], 1u);
-      buf[lofs[pl] + r] = ((unsigned long long)(g * BV_NKG + key) << 32) | (pt << 1) | (d < 0 ? 1u : 0u);
+      const uint32_t slot = lofs[pl] + atomicAdd(&rank[pl], 1u);
+      buf[slot] = PE::make(g * BV_NKG + key, (pt << 1) | (d < 0 ? 1u : 0u));
+      if constexpr (PE::narrow) bpl[slot] = (uint8_t)pl;
     };
     if (w < 8 && dR[w]) place(dR[w], ptR);
     if (dA[w]) place(dA[w], ptA);
     __syncthreads();
     const uint32_t tot = lofs[BV_PPW];
+    // at most two laps (unrolled by 8, as the compiler does with the narrow entry, the loop takes
+    // 90 VGPRs and the block has the CU to itself)
+#pragma unroll 1
     for (uint32_t i = threadIdx.x; i < tot; i += PART_CHUNK) {
-      const unsigned long long e = buf[i];
-      const uint32_t pl = ((uint32_t)(e >> 32) >> BV_FINE_BITS) & (BV_PPW - 1);
+      const E e = buf[i];
+      uint32_t pl;
+      if constexpr (PE::narrow) pl = bpl[i];
+      else pl = ((uint32_t)(e >> 32) >> BV_FINE_BITS) & (BV_PPW - 1);
       tmp[gpos[pl] + (i - lofs[pl])] = e;
     }
     __syncthreads();
@@ -551,9 +589,11 @@ __global__ void __launch_bounds__(PART_CHUNK) k_part_scatter_lds(const uint4* __
 constexpr int FINE_NT = 1024;
 constexpr uint32_t FINE_LDS = 16384;
 constexpr int FINE_FPT = FINE_LDS / FINE_NT;
-__global__ void __launch_bounds__(FINE_NT) k_fine_sort_lds(const unsigned long long* __restrict__ tmp,
+template <class E>  // tmp's entry form (PartEntry)
+__global__ void __launch_bounds__(FINE_NT) k_fine_sort_lds(const E* __restrict__ tmp,
                                                            const uint32_t* __restrict__ pstart, uint32_t ngroups,
                                                            uint32_t* __restrict__ ents, uint32_t* __restrict__ offs) {
+  using PE = PartEntry<E>;
   constexpr int NF = 1 << BV_FINE_BITS;
   __shared__ uint32_t cnt[NF];
   __shared__ uint32_t obuf[FINE_LDS];
@@ -571,15 +611,15 @@ __global__ void __launch_bounds__(FINE_NT) k_fine_sort_lds(const unsigned long l
 #pragma unroll
     for (int k = 0; k < FINE_FPT; k++) {
       const uint32_t i = threadIdx.x + (uint32_t)k * FINE_NT;
-      const unsigned long long v = i < m ? tmp[s + i] : 0ull;
-      ent[k] = (uint32_t)v;
-      br[k] = ((uint32_t)(v >> 32) & (NF - 1)) << 16;
+      const E v = i < m ? tmp[s + i] : (E)0;
+      ent[k] = PE::ref(v);
+      br[k] = PE::bin(v) << 16;
     }
 #pragma unroll
     for (int k = 0; k < FINE_FPT; k++)
       if (threadIdx.x + (uint32_t)k * FINE_NT < m) br[k] |= atomicAdd(&cnt[br[k] >> 16], 1u);
   } else {
-    for (uint32_t i = s + threadIdx.x; i < e; i += FINE_NT) atomicAdd(&cnt[(uint32_t)(tmp[i] >> 32) & (NF - 1)], 1u);
+    for (uint32_t i = s + threadIdx.x; i < e; i += FINE_NT) atomicAdd(&cnt[PE::bin(tmp[i])], 1u);
   }
   __syncthreads();
   static_assert(NF == 256, "wave 0 scans four bins per lane");
@@ -615,9 +655,9 @@ __global__ void __launch_bounds__(FINE_NT) k_fine_sort_lds(const unsigned long l
     for (uint32_t i = threadIdx.x; i < m; i += FINE_NT) ents[s + i] = obuf[i];
   } else {
     for (uint32_t i = s + threadIdx.x; i < e; i += FINE_NT) {
-      const unsigned long long x = tmp[i];
-      const uint32_t r = atomicAdd(&cnt[(uint32_t)(x >> 32) & (NF - 1)], 1u);
-      ents[s + r] = (uint32_t)x;
+      const E x = tmp[i];
+      const uint32_t r = atomicAdd(&cnt[PE::bin(x)], 1u);
+      ents[s + r] = PE::ref(x);
     }
   }
 }
@@ -695,9 +735,11 @@ __global__ void __launch_bounds__(256, MV_BUCKET_OCC) k_bv_bucket_bal(const uint
       for (int i = 0; i < 7; i++) q[i] = p[i];
     }
     precomp_cneg(pc, neg);
+    // the seven multiplications with every column summed on its own (MulOrder::split): 3 waves
+    // per SIMD do not cover the chained order's dependent low columns
     p1p1 t;
-    p3_add_precomp(t, T, pc);
-    p1p1_to_p3(T, t);
+    p3_add_precomp<MulOrder::split>(t, T, pc);
+    p1p1_to_p3<MulOrder::split>(T, t);
     if (x + 1 == nb) {  // bucket b complete (in this lane)
       emit(b, T);
       head = false;
@@ -1189,7 +1231,7 @@ struct BatchLayout {
     poff = take(nchunk * BV_NPG * 4);
     ptot = take((size_t)groups * BV_NPG * 4);
     pstart = take(((size_t)groups * BV_NPG + 1) * 4);
-    tmp = take((size_t)(BV_NWR + BV_NW) * n * 8);
+    tmp = take((size_t)(BV_NWR + BV_NW) * n * 8);  // (the narrow entry form uses half of it)
     offs = take(((size_t)groups * BV_NKG + 1) * 4);
     ents = take((size_t)(BV_NWR + BV_NW) * n * 4);
     // k_bv_bucket_bal's carries (one per lane, at most BV_NKG / 2 lanes per group)
@@ -1318,7 +1360,9 @@ hipError_t launch_msm_stage(const Knobs& kn, const uint32_t* key_idx, uint32_t n
   uint32_t* poff = (uint32_t*)(base + L.poff);
   uint32_t* ptot = (uint32_t*)(base + L.ptot);
   uint32_t* pstart = (uint32_t*)(base + L.pstart);
-  unsigned long long* tmp = (unsigned long long*)(base + L.tmp);
+  void* tmp = base + L.tmp;
+  // narrow partition entries whenever the batch's point references fit them (MV_SORT_WIDE=1: never)
+  const bool sort_narrow = !kn.sort_wide && n <= BV_NARROW_MAX_N;
   uint32_t* offs = (uint32_t*)(base + L.offs);
   uint32_t* ents = (uint32_t*)(base + L.ents);
   uint4* carry = (uint4*)(base + L.carry);
@@ -1340,9 +1384,17 @@ hipError_t launch_msm_stage(const Knobs& kn, const uint32_t* key_idx, uint32_t n
     hipLaunchKernelGGL(k_part_scan, dim3(G.count * (BV_NPG / 64)), dim3(64 * SCAN_SUB), 0, s, pcount, nchunk, G, poff,
                        ptot);
     hipLaunchKernelGGL(k_part_top, dim3(1), dim3(256), 0, s, ptot, nparts, pstart);
-    hipLaunchKernelGGL(k_part_scatter_lds, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, pcount, poff, pstart, G,
-                       agg ? 1u : 0u, n, 0u, tmp);
-    hipLaunchKernelGGL(k_fine_sort_lds, dim3(nparts), dim3(FINE_NT), 0, s, tmp, pstart, G.count, ents, offs);
+    if (sort_narrow) {
+      hipLaunchKernelGGL(k_part_scatter_lds<uint32_t>, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, pcount, poff,
+                         pstart, G, agg ? 1u : 0u, n, 0u, (uint32_t*)tmp);
+      hipLaunchKernelGGL(k_fine_sort_lds<uint32_t>, dim3(nparts), dim3(FINE_NT), 0, s, (const uint32_t*)tmp, pstart,
+                         G.count, ents, offs);
+    } else {
+      hipLaunchKernelGGL(k_part_scatter_lds<unsigned long long>, dim3(nchunk), dim3(PART_CHUNK), 0, s, scal, n, pcount,
+                         poff, pstart, G, agg ? 1u : 0u, n, 0u, (unsigned long long*)tmp);
+      hipLaunchKernelGGL(k_fine_sort_lds<unsigned long long>, dim3(nparts), dim3(FINE_NT), 0, s,
+                         (const unsigned long long*)tmp, pstart, G.count, ents, offs);
+    }
     mark(2);
     // bucket sums of the sorted entries. Equal entries per lane (at most one carry per lane):
     // 64 per lane (MV_BUCKET_BAL > 1: that many), but at least 3 waves per SIMD (196,608 lanes)

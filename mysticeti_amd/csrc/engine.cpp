@@ -484,6 +484,7 @@ const KnobDef kKnobs[] = {
     {"MV_PREP_CHAIN", &mvk::Knobs::prep_chain, K_INT, false},
     {"MV_BLK_WALK", &mvk::Knobs::blk_walk, K_ON, false},
     {"MV_BUCKET_BAL", &mvk::Knobs::bucket_bal, K_INT, false},
+    {"MV_SORT_WIDE", &mvk::Knobs::sort_wide, K_OFF, false},
     {"MV_FINAL_ROWS", &mvk::Knobs::final_rows, K_ON, false},
     {"MV_REDUCE_ROWS", &mvk::Knobs::reduce_rows, K_INT, false},
     {"MV_INDEX_TAG_BITS", &mvk::Knobs::index_tag_bits, K_INT, false},

@@ -127,12 +127,60 @@ MV_DEV void fe_reduce_scan(fe& r, Col col) {
   for (int k = 0; k < 9; k++) r.v[k] = o[k];
 }
 
-MV_DEV void fe_mul(fe& r, const fe& a, const fe& b) {
-  fe_reduce_scan(r, [&](int k, uint64_t c) {
+// The same reduction in the order of summation it had before the carry went through the MAD
+// addend: col(k) returns the 64-bit sum of column k alone (< 2^63.3), all 17 columns are
+// independent chains, a high column is folded into the low sums as it is produced (the same
+// L * 1216 and H * 9728 terms), and the ripple then runs with 64-bit adds over the finished low
+// sums (< 2^63.3 + 2^42.3 + 2^44.6 before their carry). Nine more instructions than the chained
+// order and more live registers, but no dependency between the columns' MADs: it is the faster
+// order where a kernel's occupancy does not cover one 61-MAD chain (fe_mul's MulOrder).
+template <class Col>
+MV_DEV void fe_reduce_scan_split(fe& r, Col col) {
+  uint64_t lo[9];
 #pragma unroll
-    for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) fe_mac(c, a.v[i], b.v[k - i]);
-    return c;
-  });
+  for (int k = 0; k < 9; k++) lo[k] = col(k);
+#pragma unroll
+  for (int k = 9; k < 17; k++) {
+    uint64_t c = col(k);
+    // opaque: keeps the column one 64-bit MAD chain (otherwise the compiler may also
+    // rebuild its low half from v_mul_lo_u32 products for the L * 1216 term)
+    asm("" : "+v"(c));
+    lo[k - 9] += (uint64_t)(uint32_t)c * R261;
+    lo[k - 8] += (uint64_t)(uint32_t)(c >> 32) * (8 * R261);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    r.v[k] = (uint32_t)lo[k] & M29;
+    lo[k + 1] += lo[k] >> 29;
+  }
+  r.v[8] = (uint32_t)lo[8] & M29;
+  uint64_t t0 = (uint64_t)r.v[0] + (lo[8] >> 29) * R261;  // top < 2^35
+  r.v[0] = (uint32_t)t0 & M29;
+  r.v[1] += (uint32_t)(t0 >> 29);  // < 2^29 + 2^17
+}
+
+// fe_mul's order of summation, chosen per call site (the limbs are the same integers either way:
+// tests/test_gpu_fe_mul_orders.py). chained: fe_reduce_scan, the default and fe_sq's only order;
+// it is what keeps k_bv_prep at 4 waves per SIMD. split: fe_reduce_scan_split, for
+// k_bv_bucket_bal's point addition (7 fe_mul per entry at 3 waves per SIMD).
+enum class MulOrder { chained, split };
+
+template <MulOrder O = MulOrder::chained>
+MV_DEV void fe_mul(fe& r, const fe& a, const fe& b) {
+  if constexpr (O == MulOrder::chained) {
+    fe_reduce_scan(r, [&](int k, uint64_t c) {
+#pragma unroll
+      for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) fe_mac(c, a.v[i], b.v[k - i]);
+      return c;
+    });
+  } else {
+    fe_reduce_scan_split(r, [&](int k) {
+      uint64_t c = 0;
+#pragma unroll
+      for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) c += (uint64_t)a.v[i] * b.v[k - i];
+      return c;
+    });
+  }
 }
 MV_DEV void fe_sq(fe& r, const fe& a_in) {
   // opaque limbs: otherwise the compiler rebuilds 2a from the producer's unmasked column

@@ -54,11 +54,13 @@ MV_DEV void p1p1_to_p2(p2& r, const p1p1& c) {
   fe_mul(r.Y, c.Y, c.Z);
   fe_mul(r.Z, c.Z, c.T);
 }
+// (O: the multiplications' order of summation, fe25519.h MulOrder; here and in p3_add_precomp)
+template <MulOrder O = MulOrder::chained>
 MV_DEV void p1p1_to_p3(p3& r, const p1p1& c) {
-  fe_mul(r.X, c.X, c.T);
-  fe_mul(r.Y, c.Y, c.Z);
-  fe_mul(r.Z, c.Z, c.T);
-  fe_mul(r.T, c.X, c.Y);
+  fe_mul<O>(r.X, c.X, c.T);
+  fe_mul<O>(r.Y, c.Y, c.Z);
+  fe_mul<O>(r.Z, c.Z, c.T);
+  fe_mul<O>(r.T, c.X, c.Y);
 }
 MV_DEV void p3_to_cached(cached& r, const p3& p) {
   fe d2;
@@ -103,13 +105,14 @@ MV_DEV void p3_add_cached(p1p1& r, const p3& p, const cached& q) {
   fe_sub(r.T, ZZ2, TT);     // N
 }
 // P + Q (Q precomp, Z = 1): 3 multiplications
+template <MulOrder O = MulOrder::chained>
 MV_DEV void p3_add_precomp(p1p1& r, const p3& p, const precomp& q) {
   fe PP, MM, TT, Z2, ypx, ymx;
   fe_add(ypx, p.Y, p.X);
   fe_sub(ymx, p.Y, p.X);
-  fe_mul(PP, ypx, q.ypx);
-  fe_mul(MM, ymx, q.ymx);
-  fe_mul(TT, p.T, q.xy2d);
+  fe_mul<O>(PP, ypx, q.ypx);
+  fe_mul<O>(MM, ymx, q.ymx);
+  fe_mul<O>(TT, p.T, q.xy2d);
   fe_add(Z2, p.Z, p.Z);
   fe_sub(r.X, PP, MM);
   fe_add(r.Y, PP, MM);

@@ -538,6 +538,8 @@ __global__ void __launch_bounds__(64) k_selftest(int op, const uint32_t* __restr
 //   69 fe_sub   70 fe_neg(a)   71 fe_normalize(a)   72 fe_canon(a), out words 40..47 fe_to_words(a)
 //   73 fe_sqn(a, parameter)   74 fe_invert(a)   75 feq_mul   76 feq_sqn(a, parameter)
 //   77 fer_mul   78 fer_sqn(a, parameter)   79 r4::carry(a)   80 r4::addn   81 r4::sub
+//   82 fe_mul<MulOrder::split>(a, b), the bucket kernel's order (64 is the default, chained)
+//   83 a * b^parameter by fe_mul<MulOrder::split>(r, r, b) in place
 // Point ops: P = (a, b, c, d) raw when parameter bit 11 is set, else the decoded P encoding;
 // Q is the decoded Q encoding (parameter bits 8..9 = 0), P itself (1) or P's (Y, X, T, Z) (2).
 // Parameter bits 0..7: P is doubled that many times first; bit 12: Q = p3_neg(Q) first;
@@ -620,6 +622,12 @@ __global__ void __launch_bounds__(64) k_selftest_wide(int op, const uint32_t* __
         fe_from_fer(r, rr);
         break;
       }
+      case 82: fe_mul<MulOrder::split>(r, a, b); break;
+      case 83:  // in place, the result an operand of the next call
+        r = a;
+#pragma unroll 1
+        for (int i = 0; i < nsq; i++) fe_mul<MulOrder::split>(r, r, b);
+        break;
       default: break;
     }
     if (op == 72) fe_to_words(ow, a);
