@@ -56,6 +56,8 @@
  *                          the production wave length 3, which UniversalCommitter::try_commit
  *                          (consensus/universal_committer.rs:30-90) runs for every undecided leader after
  *                          every add_blocks
+ *   mv_commit_leaders      try_commit itself: the direct rule, try_indirect_decide (:294-318) over
+ *                          BlockStore::linked_to_round (block_store.rs:306-327), and the decided prefix
  *
  * Conventions
  *   - The caller owns every buffer passed in and out; they must stay valid for the call.
@@ -555,12 +557,61 @@ mv_status mv_dag_stats(mv_ctx* ctx, uint64_t* out /* 4 */);
  * equivocate in the voting round, a quorum of blame can stand beside a leader block with enough
  * support; blame is tested first, here as in the reference, so fewer records can uncover that COMMIT.)
  * What stays with the caller: try_indirect_decide (:294-318), the longest-decided-prefix rule and
- * the genesis filter of UniversalCommitter::try_commit, and the linearizer.
+ * the genesis filter of UniversalCommitter::try_commit (mv_commit_leaders runs these), and the linearizer.
  * Requires mv_set_committee (MV_E_NO_COMMITTEE) and mv_dag_reserve (MV_E_INVALID_ARG without the
  * store). n = 0 does nothing. Results do not depend on MV_INDEX_TAG_BITS, on the order blocks were
  * delivered in, or on launch geometry. */
 mv_status mv_decide_leaders(mv_ctx* ctx, const uint64_t* leaders /* n x 2: authority, round */, uint32_t n,
                             uint64_t* out /* n x 8 */, uint64_t* stakes /* n x 3, may be NULL */);
+
+#define MV_COMMIT_KIND_NONE 0     /* info word 0: the row is not decided */
+#define MV_COMMIT_KIND_DIRECT 1   /* the direct rule gave the row's status */
+#define MV_COMMIT_KIND_INDIRECT 2 /* the indirect rule did, from the anchor of word 1 */
+#define MV_COMMIT_INCOMPLETE 1    /* info word 2, bit 0: the store lacks records this row's walk would read */
+#define MV_COMMIT_BLOCKED 2       /* bit 1: the first row three rounds up that is not SKIP is not COMMIT either */
+/* What UniversalCommitter::try_commit returns (consensus/universal_committer.rs:30-90), at wave length
+ * 3: the direct rule of mv_decide_leaders, BaseCommitter::try_indirect_decide (base_committer.rs:294-318)
+ * for the rows it leaves undecided, and the longest decided prefix. `leaders` holds the rows in the
+ * order try_commit's deque ends in (:38-72: rounds downwards, committers in reverse, push_front):
+ * ascending round, and within a round in committer order. The caller elects them and starts after its
+ * last_decided leader (:46-53). Rows not in non-decreasing round order: MV_E_INVALID_ARG.
+ * For row i = (a, r), from the last row to the first:
+ *   Direct first. The row's status under mv_decide_leaders; anything but MV_LEADER_UNDECIDED is
+ *   final, kind MV_COMMIT_KIND_DIRECT.
+ *   Anchor scan (:299-315). Otherwise the rows j > i with round_j >= r + 3, in row order: a SKIP row is
+ *   passed over, a COMMIT row is the anchor, any other row stops the scan and row i stays
+ *   MV_LEADER_UNDECIDED with MV_COMMIT_BLOCKED. Without an anchor the row stays MV_LEADER_UNDECIDED.
+ *   Reach (BlockStore::linked_to_round, block_store.rs:306-327). With the anchor's block A at round R,
+ *   reach[R] = {A}; for q = R - 1 down to r + 2, reach[q] = the records of round q that are an include
+ *   of a record in reach[q + 1]. Only includes exactly one round below the including block carry the
+ *   walk, as in the reference's loop; an empty level ends it (:322-324).
+ *   Certificates (decide_leader_from_anchor, base_committer.rs:184-224). The leader blocks are the
+ *   records with (authority, round) = (a, r); more than MV_DECIDE_MAX_LEADER_BLOCKS: MV_LEADER_OVERFLOW.
+ *   Leader block B is certified when some C in reach[r + 2] is a certificate for B, by the predicate of
+ *   mv_decide_leaders. Exactly one certified block: MV_LEADER_COMMIT of it. More than one:
+ *   MV_LEADER_CONFLICT (the reference panics, :214-216). None: MV_LEADER_SKIP -- unless the row is
+ *   incomplete. These are kind MV_COMMIT_KIND_INDIRECT.
+ *   Incomplete. The direct rule is monotone in the records; the indirect SKIP is not, since a
+ *   missing record can hide the certificate. The reference never lacks a block of a stored block's
+ *   sub-DAG ("We should have the whole sub-dag by now", :128, :166); this store does, for seeded
+ *   references and pruned rounds. A row is incomplete when r lies below the store's lowest record
+ *   round; or a record in reach[q + 1] has an include whose round is q and which has no record, for a
+ *   q of the row's walk; or a record in reach[r + 2] has an include of round r + 1 without a record; or
+ *   such an include has a record whose support for (a, r) is a reference without a record. An
+ *   incomplete row without a certified block is MV_LEADER_UNDECIDED (kind MV_COMMIT_KIND_NONE),
+ *   never SKIP; with exactly one it is still COMMIT, because missing records only remove certificates.
+ *   Every row that had an anchor reports MV_COMMIT_INCOMPLETE as it was found.
+ * The sequence (:75-90): the rows of round 0 are dropped first; *n_sequence is then the number of rows
+ * in the longest prefix whose status is MV_LEADER_COMMIT or MV_LEADER_SKIP -- the rows of round > 0,
+ * in order, up to that count.
+ * out row i: as mv_decide_leaders (words 0-5 the committed reference, 6 the status, 7 the leader
+ * blocks found). info row i: word 0 the kind, 1 the anchor's row (all ones without one), 2 the flags,
+ * 3 the records in reach[r + 2].
+ * What stays with the caller: leader election, last_decided, and the linearizer.
+ * Requirements and refusals as mv_decide_leaders; n = 0 sets *n_sequence = 0. The call leaves no
+ * state behind: a later mv_decide_leaders or mv_commit_leaders reads the store alone. */
+mv_status mv_commit_leaders(mv_ctx* ctx, const uint64_t* leaders /* n x 2, in sequence order */, uint32_t n,
+                            uint64_t* out /* n x 8 */, uint64_t* info /* n x 4 */, uint64_t* n_sequence);
 
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
@@ -658,6 +709,10 @@ mv_status mv_dev_connect_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, u
  * The rows are read back to be sorted by round; `stream` is synchronised. */
 mv_status mv_dev_decide_leaders(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_out,
                                 uint64_t* d_stakes /* may be NULL */, void* stream);
+/* mv_commit_leaders with the leader rows and the results in HBM of the context's first device;
+ * *n_sequence on the host. The rows are read back to be checked and grouped; `stream` is synchronised. */
+mv_status mv_dev_commit_leaders(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_out,
+                                uint64_t* d_info, uint64_t* n_sequence, void* stream);
 /* crc32fast::hash of n strings of device buffer d_buf at d_off/d_len (device arrays) -> d_out. Enqueue only. */
 mv_status mv_dev_crc32(mv_ctx* ctx, int device, const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len,
                        uint32_t n, uint32_t* d_out, void* stream);

@@ -36,6 +36,9 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.dag_reserve, Engine.dag_prune, Engine.dag_stats, Engine.decide_leaders (and dev_decide_leaders)
                            the edges of the blocks connect_blocks stored, kept on the GPU, and
                            BaseCommitter::try_direct_decide over them (base_committer.rs:323-357)
+  Engine.commit_leaders (and dev_commit_leaders)
+                           UniversalCommitter::try_commit over them (universal_committer.rs:30-90): the direct
+                           rule, try_indirect_decide (base_committer.rs:294-318) and the decided prefix
   Engine.dev_accept_blocks, Engine.dev_connect_blocks, Engine.dev_index_insert
                            the same on buffers already in HBM (a replay's rows go in at a stride)
   frame_messages           the frame and message walk alone, on the host, for one stream
@@ -76,6 +79,7 @@ EXPORTS = [
     "mv_accept_blocks", "mv_dev_accept_blocks", "mv_dev_index_insert",
     "mv_index_insert_stored", "mv_connect_blocks", "mv_dev_connect_blocks", "mv_pending_reserve", "mv_pending_stats",
     "mv_dag_reserve", "mv_dag_prune", "mv_dag_stats", "mv_decide_leaders", "mv_dev_decide_leaders",
+    "mv_commit_leaders", "mv_dev_commit_leaders",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
@@ -98,6 +102,10 @@ E_INVALID_ARG, E_NO_COMMITTEE = -1, -4
 LEADER_STATUS = ["UNDECIDED", "COMMIT", "SKIP", "CONFLICT", "OVERFLOW"]
 LEADER_UNDECIDED, LEADER_COMMIT, LEADER_SKIP, LEADER_CONFLICT, LEADER_OVERFLOW = range(5)
 DECIDE_MAX_LEADER_BLOCKS = 8
+# mv_commit_leaders: word 0 of an info row, the bits of word 2, word 1 without an anchor
+COMMIT_KIND_NONE, COMMIT_KIND_DIRECT, COMMIT_KIND_INDIRECT = range(3)
+COMMIT_INCOMPLETE, COMMIT_BLOCKED = 1, 2
+COMMIT_NO_ANCHOR = 0xFFFFFFFFFFFFFFFF
 WAL_MAP_BITS, WAL_MAP_BITS_TEST = 24, 16  # wal.rs:95-103
 # batch path stages, the block pipeline's, the WAL replay's (mv_stage_times order, MV_NSTAGES)
 STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "hash", "verify", "verdict", "wal_walk",
@@ -200,6 +208,8 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dag_stats.argtypes = [vp, vp]
     lib.mv_decide_leaders.argtypes = [vp, vp, u32, vp, vp]
     lib.mv_dev_decide_leaders.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, vp]
+    lib.mv_commit_leaders.argtypes = [vp, vp, u32, vp, vp, vp]
+    lib.mv_dev_commit_leaders.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, vp, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     lib.mv_host_free.argtypes = [vp, vp]
     lib.mv_host_free.restype = None
@@ -828,6 +838,27 @@ class Engine:
         self._check(self.lib.mv_dev_decide_leaders(self.ctx, device, ptr(d_leaders), d_leaders.shape[0], ptr(d_out),
                                                    ptr(d_stakes), vp(stream_handle or None)), "mv_dev_decide_leaders")
 
+    def commit_leaders(self, leaders) -> "Committed":
+        """The direct and the indirect decision rule and the decided prefix (mv_commit_leaders) for the
+        (authority, round) rows of `leaders`, which stand in sequence order: ascending round."""
+        rows = np.ascontiguousarray(np.asarray(leaders, dtype=np.uint64).reshape(-1, 2))
+        n = rows.shape[0]
+        out, info = np.zeros((n, 8), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        n_seq = ctypes.c_uint64(0)
+        self._check(self.lib.mv_commit_leaders(self.ctx, _p(rows) if n else None, n, _p(out) if n else None,
+                                               _p(info) if n else None, ctypes.byref(n_seq)), "mv_commit_leaders")
+        return Committed(out, info, int(n_seq.value), rows)
+
+    def dev_commit_leaders(self, device: int, d_leaders, d_out, d_info, stream_handle: int = 0) -> int:
+        """mv_dev_commit_leaders on torch device tensors: d_leaders (n, 2), d_out (n, 8), d_info (n, 4),
+        all int64. Returns the sequence's length."""
+        vp = ctypes.c_void_p
+        n_seq = ctypes.c_uint64(0)
+        self._check(self.lib.mv_dev_commit_leaders(self.ctx, device, vp(d_leaders.data_ptr()), d_leaders.shape[0],
+                                                   vp(d_out.data_ptr()), vp(d_info.data_ptr()), ctypes.byref(n_seq),
+                                                   vp(stream_handle or None)), "mv_dev_commit_leaders")
+        return int(n_seq.value)
+
     def dev_index_insert(self, device: int, d_words, stride_words: int, n: int, state: int = REF_HAVE,
                          stream_handle: int = 0, word_offset: int = 0):
         """mv_dev_index_insert: reference i is the six int64 words of torch device tensor d_words at
@@ -1074,6 +1105,23 @@ class Decided:
         if int(self.rows[i, 6]) != LEADER_COMMIT:
             return None
         return int(self.rows[i, 0]), int(self.rows[i, 1]), self.rows[i, 2:6].astype("<u8").tobytes()
+
+
+class Committed(Decided):
+    """Result of Engine.commit_leaders (mv_commit_leaders): rows as Decided's; info (n, 4) uint64 --
+    the COMMIT_KIND_*, the anchor's row or COMMIT_NO_ANCHOR, the COMMIT_INCOMPLETE / COMMIT_BLOCKED
+    bits, the records the walk reached in the decision round -- and n_sequence, the length of the
+    decided prefix over the rows of round > 0. leaders: the (n, 2) rows the call was given."""
+
+    def __init__(self, rows, info, n_sequence, leaders):
+        super().__init__(rows, None)
+        self.info, self.n_sequence, self.leaders = info, n_sequence, leaders
+        self.kind, self.flags = info[:, 0].astype(np.int64), info[:, 2].astype(np.int64)
+
+    def sequence(self):
+        """The decided rows, in order: (row, status)."""
+        rows = [i for i in range(self.leaders.shape[0]) if int(self.leaders[i, 1]) > 0][:self.n_sequence]
+        return [(i, int(self.status[i])) for i in rows]
 
 
 class WalReplay:

@@ -200,8 +200,9 @@ struct Device {
       DevBuf rec, inc, map;
       uint64_t nb = 0, ni = 0, cap_b = 0, cap_i = 0, map_slots = 0;
       // a connect call's row -> record scratch, a prune's new bases, and a decide call's sorted
-      // rows, per-row state, per-record lists, supports and results
-      DevBuf src, newbase, lead, state, lists, sup, res;
+      // rows, per-row state, per-record lists, supports and results; a commit call's certificate
+      // masks, per-row chain state, per-job marks and the records of its round span
+      DevBuf src, newbase, lead, state, lists, sup, res, cmask, cm, marks, span;
     } dag;
   } index;
 

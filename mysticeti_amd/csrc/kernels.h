@@ -456,7 +456,12 @@ constexpr int IX_CTL_HAVE = 0, IX_CTL_WANTED = 1, IX_CTL_MAXPROBE = 2, IX_CTL_RE
               // and decision records a decide call picked
               IX_CTL_DG_NI = IX_CTL_PB_END, IX_CTL_DG_NLO = IX_CTL_DG_NI + 1, IX_CTL_DG_HI = IX_CTL_DG_NI + 2,
               IX_CTL_DG_NVOTE = IX_CTL_DG_NI + 3, IX_CTL_DG_NDEC = IX_CTL_DG_NI + 4, IX_CTL_DG_NB = IX_CTL_DG_NI + 5,
-              IX_CTL_WORDS = IX_CTL_DG_NI + 8;
+              // a commit call's pass: the walk jobs its chain step emitted, the highest anchor round, the
+              // max of ~(lowest target round), the rows the pass moved; and the sequence's length
+              IX_CTL_CM_NJOBS = IX_CTL_DG_NI + 8, IX_CTL_CM_QHI = IX_CTL_DG_NI + 9, IX_CTL_CM_NQLO = IX_CTL_DG_NI + 10,
+              IX_CTL_CM_MOVED = IX_CTL_DG_NI + 11, IX_CTL_CM_NSEQ = IX_CTL_DG_NI + 12,
+              IX_CTL_CM_NSPAN = IX_CTL_DG_NI + 13,  // the records of the rounds a commit call's levels read
+              IX_CTL_WORDS = IX_CTL_DG_NI + 16;
 uint64_t index_groups(uint64_t n);  // workgroups of the per-item kernels: wgcount / wgbase hold one word each
 hipError_t launch_index_scan(const uint64_t* wgcount, uint64_t nwg, uint64_t* wgbase, uint64_t* total, hipStream_t s);
 // one insert round (k_ix_claim, k_ix_fill, k_ix_settle) of n items towards `state`; item: n words
@@ -590,6 +595,8 @@ struct DecideState {  // zeroed by the caller except vpos / vlist / dlist / sup
   uint32_t* vlist;      // the voting records, the decision records
   uint32_t* dlist;
   uint64_t* sup;        // per (place in vlist, row of that round): the supported slot, DG_NO_SLOT for none
+  uint8_t* cmask;       // null for a decide call; a commit call: per (place in dlist, row of that round) the
+                        // candidates the decision record certifies, bit c for candidate c (zeroed by the caller)
 };
 // k_dg_pick: vpos, vlist, dlist, the candidates; ctl[IX_CTL_DG_NVOTE], ctl[IX_CTL_DG_NDEC]
 hipError_t launch_decide_pick(const DagStore& d, uint64_t nb, const DecideIn& in, const DecideState& st,
@@ -599,4 +606,42 @@ hipError_t launch_decide_rule(const IndexTable& t, const DagStore& d, uint64_t n
                               const DecideState& st, uint64_t nvote, uint64_t ndec, const uint64_t* stakes,
                               uint32_t n_auth, uint64_t quorum_thr, uint64_t* out, uint64_t* stakes_out, uint64_t* ctl,
                               hipStream_t s);
+
+// One commit call (mv_commit_leaders; kernels: index.hip) on top of a decide call's DecideIn /
+// DecideState and its out rows, which must be in non-decreasing round order (l_row[k] = k). All
+// arrays are per row unless said otherwise.
+struct CommitState {
+  uint32_t* fin;        // 0: the direct rule left the row UNDECIDED and nothing ended it yet; 1: final
+  uint32_t* act;        // what a pass's chain step found for a row: CM_ACT_*
+  uint32_t* anchor;     // the anchor's row (CM_ACT_WALK)
+  uint64_t* cslot;      // the slot of a COMMIT row's block, DG_NO_SLOT otherwise
+  uint32_t* job_id;     // per anchor row: its walk job in this pass, DG_NONE without one
+  uint64_t* job_low;    // per anchor row: the lowest round its walk has to reach
+  uint64_t* job_miss;   // per anchor row: 1 + the highest round at which an include of the walk had no record
+  uint32_t* jobs;       // per job: its anchor's row
+  uint32_t* marks;      // per job: a bitmap over the records (mark_words words each), made per pass
+  uint64_t mark_words;
+  uint32_t* span;       // the records of the rounds the call's levels can read (per call)
+};
+constexpr uint32_t CM_ACT_NONE = 0, CM_ACT_UNDECIDED = 1, CM_ACT_BLOCKED = 2, CM_ACT_WALK = 3;
+constexpr uint32_t CM_CLAIMED = 0xfffffffeu;
+// after launch_decide_rule: fin, cslot and the info rows of the rows the direct rule decided
+hipError_t launch_commit_init(const IndexTable& t, const DecideIn& in, const DecideState& st, const CommitState& cs,
+                              const uint64_t* out, uint64_t* info, uint64_t* ctl, hipStream_t s);
+// one pass's chain step: act, anchor, the jobs; ctl[IX_CTL_CM_NJOBS / _QHI / _NQLO / _MOVED] (zeroed by the caller,
+// as job_id (all ones), job_low (all ones) and job_miss (0) are)
+hipError_t launch_commit_chain(const DecideIn& in, const CommitState& cs, const uint64_t* out, uint64_t* ctl, hipStream_t s);
+// span = the records of rounds lo..hi; ctl[IX_CTL_CM_NSPAN] = how many (wg: 2 x index_groups(nb))
+hipError_t launch_commit_span(const DagStore& d, uint64_t nb, uint64_t lo, uint64_t hi, uint32_t* span, uint64_t* wg,
+                              uint64_t* ctl, hipStream_t s);
+// the anchors' records into the (zeroed) marks, then one launch over the span per level of `levels` (descending)
+hipError_t launch_commit_reach(const IndexTable& t, const DagStore& d, uint64_t nb, const DecideIn& in,
+                               const CommitState& cs, uint64_t njobs, uint64_t nspan, const uint64_t* levels,
+                               uint64_t n_levels, uint64_t* ctl, hipStream_t s);
+// the rows the chain step moved: status, committed reference, info, fin
+hipError_t launch_commit_resolve(const IndexTable& t, const DagStore& d, uint64_t nb, const DecideIn& in,
+                                 const DecideState& st, const CommitState& cs, uint64_t nvote, uint64_t ndec, uint64_t njobs,
+                                 uint64_t* out, uint64_t* info, uint64_t* ctl, hipStream_t s);
+// ctl[IX_CTL_CM_NSEQ] = the rows of the longest prefix of COMMIT / SKIP rows among those of round > 0
+hipError_t launch_commit_prefix(const DecideIn& in, const uint64_t* out, uint64_t* ctl, hipStream_t s);
 }  // namespace mvk

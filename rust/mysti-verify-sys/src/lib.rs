@@ -43,6 +43,11 @@ pub const MV_LEADER_SKIP: u64 = 2;
 pub const MV_LEADER_CONFLICT: u64 = 3;
 pub const MV_LEADER_OVERFLOW: u64 = 4;
 pub const MV_DECIDE_MAX_LEADER_BLOCKS: u64 = 8;
+pub const MV_COMMIT_KIND_NONE: u64 = 0;
+pub const MV_COMMIT_KIND_DIRECT: u64 = 1;
+pub const MV_COMMIT_KIND_INDIRECT: u64 = 2;
+pub const MV_COMMIT_INCOMPLETE: u64 = 1;
+pub const MV_COMMIT_BLOCKED: u64 = 2;
 
 pub const MV_SIG_OK: u8 = 0;
 pub const MV_SIG_INVALID: u8 = 1;
@@ -155,6 +160,10 @@ extern "C" {
     pub fn mv_decide_leaders(ctx: *mut mv_ctx, leaders: *const u64, n: u32, out: *mut u64, stakes: *mut u64) -> i32;
     pub fn mv_dev_decide_leaders(ctx: *mut mv_ctx, device: i32, d_leaders: *const u64, n: u32, d_out: *mut u64,
                                  d_stakes: *mut u64, stream: *mut c_void) -> i32;
+    pub fn mv_commit_leaders(ctx: *mut mv_ctx, leaders: *const u64, n: u32, out: *mut u64, info: *mut u64,
+                             n_sequence: *mut u64) -> i32;
+    pub fn mv_dev_commit_leaders(ctx: *mut mv_ctx, device: i32, d_leaders: *const u64, n: u32, d_out: *mut u64,
+                                 d_info: *mut u64, n_sequence: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_dev_index_insert(ctx: *mut mv_ctx, device: i32, d_words: *const u64, stride_words: u64, n: u64,
                                state: u32, stream: *mut c_void) -> i32;
     pub fn mv_dev_verify_frames(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,

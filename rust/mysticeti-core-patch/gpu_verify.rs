@@ -307,6 +307,32 @@ impl GpuVerifier {
         ensure!(rc == sys::MV_OK, "mv_decide_leaders: {}", self.last_error());
         Ok(d)
     }
+
+    /// UniversalCommitter::try_commit (consensus/universal_committer.rs:30-90) on the GPU
+    /// (mv_commit_leaders): the direct rule, try_indirect_decide and the decided prefix for the
+    /// elected leaders (authority, round) of `leaders`, which stand in the order try_commit's deque
+    /// ends in: ascending round, within a round in committer order, after last_decided. The caller
+    /// elects the leaders, keeps last_decided and runs the linearizer on the first `n_sequence`
+    /// rows of round > 0; a row with MV_COMMIT_INCOMPLETE it decides itself once the store holds
+    /// the missing blocks.
+    pub fn commit_leaders(&self, leaders: &[(u64, u64)]) -> eyre::Result<Committed> {
+        let n = leaders.len();
+        let flat: Vec<u64> = leaders.iter().flat_map(|&(a, r)| [a, r]).collect();
+        let mut c = Committed { rows: vec![0u64; 8 * n], info: vec![0u64; 4 * n], n_sequence: 0 };
+        let rc = unsafe {
+            sys::mv_commit_leaders(self.ctx, flat.as_ptr(), n as u32, c.rows.as_mut_ptr(), c.info.as_mut_ptr(),
+                                   &mut c.n_sequence)
+        };
+        ensure!(rc == sys::MV_OK, "mv_commit_leaders: {}", self.last_error());
+        Ok(c)
+    }
+}
+
+/// Result of `GpuVerifier::commit_leaders` (layout: include/mysti_verify.h, mv_commit_leaders).
+pub struct Committed {
+    pub rows: Vec<u64>,  // eight words per leader, as Decided's
+    pub info: Vec<u64>,  // four per leader: MV_COMMIT_KIND_*, the anchor's row or u64::MAX, the flags, the reach
+    pub n_sequence: u64, // the decided prefix over the rows of round > 0
 }
 
 /// Result of `GpuVerifier::decide_leaders` (layout: include/mysti_verify.h, mv_decide_leaders).
