@@ -32,6 +32,9 @@
  *                          highest_round and last_seen_by_authority (:398-404, 424-432), and the positions
  *                          RecoveredStateBuilder wants (state.rs:39-59); also StatementBlock::verify of
  *                          every block, which the reference's replay skips
+ *   mv_wal_recover         that replay, and the replayed blocks as stored blocks with their edges in
+ *                          the DAG store: what BlockStore::open with add_unloaded (block_store.rs:398-404)
+ *                          leaves for BaseCommitter to read after a restart
  *   mv_wal_layout          WalWriter::writev position arithmetic (wal.rs:150-188), host only
  *   mv_frame_blocks        the block byte strings of received NetworkMessage frames
  *                          (Network::handle_read_stream, network.rs:400-447), host only
@@ -502,9 +505,10 @@ mv_status mv_pending_stats(mv_ctx* ctx, uint64_t* out /* 4 */);
  * reserve, mv_connect_blocks does what it did before, launch for launch. The store grows
  * geometrically, also under the device-buffer connect call (which synchronises anyway);
  * mv_index_clear empties it, mv_destroy frees it, a rebuild of the index re-resolves its slots.
- * References seeded with mv_index_insert_stored / mv_dev_index_insert (genesis, a replay's rows)
- * have no record: seeding edges is out of scope. That is safe because the rule below is monotone
- * in the records (see mv_decide_leaders). */
+ * References seeded with mv_index_insert_stored / mv_dev_index_insert (genesis, a replay's rows
+ * seeded that way) have no record; a replay's rows get theirs from mv_wal_recover /
+ * mv_dev_dag_seed_rows. A missing record is safe because the rule below is monotone in the records
+ * (see mv_decide_leaders). */
 mv_status mv_dag_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t includes);
 /* Drops the records of rounds below `round` by stable compaction: BlockStore::cleanup /
  * unload_below_round (block_store.rs:207-218, 374-390) for this store. The index entries stay
@@ -613,6 +617,48 @@ mv_status mv_decide_leaders(mv_ctx* ctx, const uint64_t* leaders /* n x 2: autho
 mv_status mv_commit_leaders(mv_ctx* ctx, const uint64_t* leaders /* n x 2, in sequence order */, uint32_t n,
                             uint64_t* out /* n x 8 */, uint64_t* info /* n x 4 */, uint64_t* n_sequence);
 
+/* ---- seeding the DAG store from a replayed WAL ----
+ * mv_wal_replay, then one seed call over all its rows while the image is still in device memory:
+ * the blocks of a WAL become stored blocks with records, which is what makes a replayed block
+ * visible to BaseCommitter (replaces: BlockStore::open with add_unloaded, block_store.rs:50-116,
+ * 398-404, and the recovered store Core::open hands to the committer, core.rs:97-113). Without it a
+ * restarted context's store is empty and every leader whose rounds touch a replayed block stays
+ * MV_LEADER_UNDECIDED with MV_COMMIT_INCOMPLETE.
+ * Every output of mv_wal_replay is written as mv_wal_replay writes it. Then, over all *n_blocks rows
+ * (whatever cap_blocks is) and their verdicts (computed whether or not blk_status is NULL), in row
+ * order:
+ *  1. References. The reference of every row (words 3..8) rises to MV_REF_STORED, whatever the row's
+ *     verdict: the reference stores every block of its WAL without verifying it. seeded[0] = the rows.
+ *  2. Records. A row gets a record in the DAG store when all of these hold: its verdict is
+ *     MV_BLOCK_OK (both decision rules rest on "a verified block's includes all have a lower round";
+ *     a genesis row is MV_BLOCK_GENESIS and gets none); its round is >= floor_round (the store holds
+ *     what mv_dag_prune(floor_round) would have left; 0 keeps everything); it is the first row of the
+ *     call, in row order, with its reference, and that reference has no record before the call; and
+ *     its bincode fits the image: length >= 64, offset + length <= size, and 64 + 56 k <= length for
+ *     the include count k at byte 56. Only a caller's mismatched arrays can break the last for an OK
+ *     row: such a row gets no record, is counted in seeded[4], and its bytes are never an address.
+ *     Records are appended behind those there, in row order -- WAL order is the order in which blocks
+ *     became stored in the life before, as connected-row order is in this one -- with the fields a
+ *     connect call writes. seeded[1] = the records appended, seeded[2] = their includes.
+ *  3. Includes. The includes of a record row (56 bytes each from byte 64 of its block, at any byte
+ *     alignment) are resolved to their entries. An include that is a row of the same call resolves to
+ *     that row's entry wherever the row stands. An include with no entry after step 1 is entered as
+ *     MV_REF_WANTED, each once, as step 5 of mv_accept_blocks enters includes, so mv_index_wanted
+ *     lists it; seeded[3] counts them. A WAL the reference wrote yields 0: anything else tells the
+ *     caller that its WAL is not self-contained, and the rows near the gap read MV_COMMIT_INCOMPLETE.
+ * A block suspended earlier that waits for a reference this call raised is released by the next
+ * mv_connect_blocks sweep (n = 0), as after mv_index_insert_stored. mv_dag_prune, rebuilds of the
+ * index and later connect calls treat seeded records like any others.
+ * Grows the index and the DAG store as needed. Requires mv_set_committee (MV_E_NO_COMMITTEE) and
+ * mv_dag_reserve (MV_E_INVALID_ARG without the store; nothing is replayed then). A WAL without block
+ * rows seeds nothing. After MV_E_HIP or MV_E_ALLOC from the seeding the caller empties index and
+ * store with mv_index_clear and seeds again, as after a failed connect call. */
+mv_status mv_wal_recover(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
+                         uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap, uint64_t* count,
+                         uint64_t* blk_rows /* cap_blocks x 10 */, uint8_t* blk_status /* cap_blocks, may be NULL */,
+                         uint64_t cap_blocks, uint64_t* n_blocks, uint64_t* summary /* 3 */,
+                         uint64_t* last_seen /* committee size */, uint64_t floor_round, uint64_t* seeded /* 5 */);
+
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
  * library's stream for that device). They enqueue work and return without synchronising. */
@@ -695,6 +741,22 @@ mv_status mv_dev_accept_blocks(mv_ctx* ctx, int device, const uint8_t* d_buf, ui
  * rounds than the call enqueues ahead; it then surfaces as MV_E_HIP from the next index call. */
 mv_status mv_dev_index_insert(mv_ctx* ctx, int device, const uint64_t* d_words, uint64_t stride_words, uint64_t n,
                               uint32_t state, void* stream);
+/* The seed call of mv_wal_recover (steps 1-3 there: BlockStore::open with add_unloaded, block_store.rs:50-116,
+ * 398-404) on the rows of an mv_dev_wal_replay, straight from HBM: d_wal / size are that call's image, d_blk_rows
+ * (n_rows x 10 words) and d_blk_status (n_rows) its block rows and their verdicts; `seeded` (5 words) is
+ * written on the host. For a caller that uses the DAG store it takes the place of
+ * mv_dev_index_insert(d_blk_rows + 3, 10, n_rows, MV_REF_STORED), which raises the references alone.
+ * d_wal and d_blk_rows are 8-byte aligned (MV_E_INVALID_ARG otherwise, as mv_dev_wal_replay). A row's
+ * offset and length are checked against `size` before a byte is read. Synchronises `stream`: the
+ * include total depends on the data. It can grow neither the index nor the DAG store:
+ * MV_E_INDEX_FULL, decided before the first insert with index and store unchanged, when n_rows plus
+ * the includes of the rows that may get a record may not fit the index at a load of 1/2
+ * (mv_index_reserve), or those rows and their includes may not fit the store (mv_dag_reserve).
+ * MV_E_NO_COMMITTEE without a committee, MV_E_INVALID_ARG without mv_dag_reserve; n_rows = 0 does
+ * nothing. */
+mv_status mv_dev_dag_seed_rows(mv_ctx* ctx, int device, const uint8_t* d_wal, uint64_t size,
+                               const uint64_t* d_blk_rows /* n_rows x 10 */, const uint8_t* d_blk_status /* n_rows */,
+                               uint64_t n_rows, uint64_t floor_round, uint64_t* seeded /* 5, host */, void* stream);
 /* mv_connect_blocks on blocks already in HBM, as mv_dev_accept_blocks is to mv_accept_blocks: every
  * array is device memory, *n_missing and *n_connected are written on the host, `stream` is
  * synchronised. It can grow neither the index nor the suspended-block store: MV_E_INDEX_FULL, decided

@@ -79,7 +79,7 @@ EXPORTS = [
     "mv_accept_blocks", "mv_dev_accept_blocks", "mv_dev_index_insert",
     "mv_index_insert_stored", "mv_connect_blocks", "mv_dev_connect_blocks", "mv_pending_reserve", "mv_pending_stats",
     "mv_dag_reserve", "mv_dag_prune", "mv_dag_stats", "mv_decide_leaders", "mv_dev_decide_leaders",
-    "mv_commit_leaders", "mv_dev_commit_leaders",
+    "mv_commit_leaders", "mv_dev_commit_leaders", "mv_wal_recover", "mv_dev_dag_seed_rows",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
@@ -188,6 +188,8 @@ def load_library(path: str = LIB_PATH):
     lib.mv_wal_replay.argtypes = [vp, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp]
     lib.mv_dev_wal_replay.argtypes = [vp, ctypes.c_int, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp,
                                       vp, vp]
+    lib.mv_wal_recover.argtypes = [vp, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, vp]
+    lib.mv_dev_dag_seed_rows.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u64, u64, vp, vp]
     lib.mv_dev_crc32.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, vp, vp]
     lib.mv_index_reserve.argtypes = [vp, u64]
     lib.mv_index_clear.argtypes = [vp]
@@ -600,7 +602,7 @@ class Engine:
         return cnt.value
 
     def wal_replay(self, image, end_pos: Optional[int] = None, map_bits: int = WAL_MAP_BITS,
-                   cap: Optional[int] = None, cap_blocks: Optional[int] = None) -> "WalReplay":
+                   cap: Optional[int] = None, cap_blocks: Optional[int] = None, _recover_floor: Optional[int] = None):
         """The replay loop of BlockStore::open (mv_wal_replay, block_store.rs:50-116) over a WAL image
         (bytes / uint8 array) up to the writer position end_pos (default: its length). Needs
         set_committee. Returns a WalReplay: the entries as wal_verify gives them (the last one
@@ -626,11 +628,38 @@ class Engine:
         summary = np.zeros(3, dtype=np.uint64)
         seen = np.zeros(max(n_auth, 1), dtype=np.uint64)
         cnt, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._check(self.lib.mv_wal_replay(self.ctx, _p(img) if size else None, size, end, map_bits, _p(pos), _p(tag),
-                                           _p(ln), _p(st), cap, ctypes.byref(cnt), _p(rows), _p(bst), cap_blocks,
-                                           ctypes.byref(nb), _p(summary), _p(seen)), "mv_wal_replay")
+        args = (self.ctx, _p(img) if size else None, size, end, map_bits, _p(pos), _p(tag), _p(ln), _p(st), cap,
+                ctypes.byref(cnt), _p(rows), _p(bst), cap_blocks, ctypes.byref(nb), _p(summary), _p(seen))
+        seeded = np.zeros(5, dtype=np.uint64)
+        if _recover_floor is None:
+            self._check(self.lib.mv_wal_replay(*args), "mv_wal_replay")
+        else:
+            self._check(self.lib.mv_wal_recover(*args, int(_recover_floor), _p(seeded)), "mv_wal_recover")
         n, b = min(cnt.value, cap), min(nb.value, cap_blocks)
-        return WalReplay(pos[:n], tag[:n], ln[:n], st[:n], rows[:b], bst[:b], summary, seen[:n_auth], cnt.value, nb.value)
+        out = WalReplay(pos[:n], tag[:n], ln[:n], st[:n], rows[:b], bst[:b], summary, seen[:n_auth], cnt.value, nb.value)
+        return out if _recover_floor is None else (out, Seeded(*(int(x) for x in seeded)))
+
+    def wal_recover(self, image, end_pos: Optional[int] = None, map_bits: int = WAL_MAP_BITS, floor_round: int = 0,
+                    cap: Optional[int] = None, cap_blocks: Optional[int] = None) -> Tuple["WalReplay", "Seeded"]:
+        """wal_replay, then the replayed blocks become stored blocks with records in the DAG store
+        (mv_wal_recover: BlockStore::open with add_unloaded, block_store.rs:398-404). Needs set_committee
+        and dag_reserve. floor_round: rows of lower rounds get no record, as after dag_prune. Returns
+        the WalReplay that wal_replay returns and a Seeded."""
+        return self.wal_replay(image, end_pos, map_bits, cap, cap_blocks, _recover_floor=int(floor_round))
+
+    def dev_dag_seed_rows(self, device: int, d_img, size: int, d_rows, d_blk_status, n_rows: Optional[int] = None,
+                          floor_round: int = 0, stream_handle: int = 0, img_ptr: Optional[int] = None) -> "Seeded":
+        """mv_dev_dag_seed_rows on torch device tensors: the image, rows ((n, 10) int64) and block
+        verdicts (uint8) of a dev_wal_replay. Synchronises the stream. Raises MvError with code
+        E_INDEX_FULL when the reserved index or the reserved DAG store has no room (both are unchanged).
+        img_ptr overrides d_img's address."""
+        vp = ctypes.c_void_p
+        n = d_rows.shape[0] if n_rows is None else int(n_rows)
+        seeded = np.zeros(5, dtype=np.uint64)
+        self._check(self.lib.mv_dev_dag_seed_rows(
+            self.ctx, device, vp(img_ptr) if img_ptr is not None else vp(d_img.data_ptr()), int(size), vp(d_rows.data_ptr()),
+            vp(d_blk_status.data_ptr()), n, int(floor_round), _p(seeded), vp(stream_handle or None)), "mv_dev_dag_seed_rows")
+        return Seeded(*(int(x) for x in seeded))
 
     def dev_wal_replay(self, device: int, d_img, size: int, end_pos: int, map_bits: int, d_pos, d_tag, d_len,
                        d_status, d_rows, d_blk_status, d_summary, d_last_seen, stream_handle: int = 0,
@@ -1088,6 +1117,18 @@ class DagStats:
 
     def __init__(self, records, includes, lowest_round, highest_round):
         self.records, self.includes, self.lowest_round, self.highest_round = records, includes, lowest_round, highest_round
+
+
+class Seeded:
+    """What a seed call did (mv_wal_recover, mv_dev_dag_seed_rows): the rows whose references rose to
+    REF_STORED, the records appended to the DAG store and their includes, the includes entered as
+    REF_WANTED (0 for a self-contained WAL), and the OK rows whose bytes did not fit the image."""
+
+    def __init__(self, rows, records, includes, wanted, misfits):
+        self.rows, self.records, self.includes, self.wanted, self.misfits = rows, records, includes, wanted, misfits
+
+    def words(self):
+        return [self.rows, self.records, self.includes, self.wanted, self.misfits]
 
 
 class Decided:

@@ -458,6 +458,12 @@ mv_status enqueue_blocks(mv_ctx* ctx, Device& dev, const uint8_t* d_buf, uint64_
                          hipStream_t s, DevBuf* own = nullptr, Device::BlkAux* own_aux = nullptr);
 std::vector<uint64_t> balanced_cuts(const uint64_t* w, uint64_t n, uint32_t parts);
 
+// engine_index.cpp: one seed call (mv_dev_dag_seed_rows) on stream s, which it synchronises; the image, the
+// rows and their block verdicts are device memory, seeded (5 words) is the host's
+mv_status dag_seed_run(mv_ctx* ctx, Device& dev, const uint8_t* d_img, uint64_t size, const uint64_t* d_rows,
+                       const uint8_t* d_status, uint64_t n, uint64_t floor_round, bool can_grow, hipStream_t s,
+                       uint64_t* seeded);
+
 // engine_online.cpp
 bool online_eligible(mv_ctx* ctx, uint32_t n, uint64_t bytes, uint64_t longest);
 mv_status online_verify(mv_ctx* ctx, Device& dev, const uint8_t* buf, const uint64_t* off, const uint64_t* len,

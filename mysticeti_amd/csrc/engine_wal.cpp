@@ -244,18 +244,22 @@ bool replay_args_ok(const void* img, uint64_t size, uint32_t map_bits, const voi
 }
 }  // namespace
 
-mv_status mv_wal_replay(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
-                        uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap, uint64_t* count,
-                        uint64_t* blk_rows, uint8_t* blk_status, uint64_t cap_blocks, uint64_t* n_blocks,
-                        uint64_t* summary, uint64_t* last_seen) {
+// mv_wal_replay, and with `seeded` mv_wal_recover: the same replay, then one seed call over all its
+// rows while image, rows and verdicts are still in the device's own buffers
+static mv_status wal_replay_host(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
+                                 uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap, uint64_t* count,
+                                 uint64_t* blk_rows, uint8_t* blk_status, uint64_t cap_blocks, uint64_t* n_blocks,
+                                 uint64_t* summary, uint64_t* last_seen, uint64_t floor_round, uint64_t* seeded) {
   if (!ctx || !replay_args_ok(wal, size, map_bits, pos, tag, len, status, cap, count, blk_rows, cap_blocks, n_blocks,
                               summary, last_seen))
     return set_err(ctx, MV_E_INVALID_ARG, "bad wal replay args");
   *count = 0;
   *n_blocks = 0;
+  if (seeded) memset(seeded, 0, 5 * sizeof(uint64_t));
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!committee_ready(ctx)) return set_err(ctx, MV_E_NO_COMMITTEE, "mv_set_committee first");
   Device& dev = ctx->devs[0];  // one image, one device
+  if (seeded && !dev.index.dag.on) return set_err(ctx, MV_E_INVALID_ARG, "mv_dag_reserve first");
   HIPCHK(ctx, hipSetDevice(dev.id));
   reap_idle(ctx, dev);
   hipStream_t s = dev.stream;
@@ -288,7 +292,28 @@ mv_status mv_wal_replay(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t
   HIPCHK(ctx, hipStreamSynchronize(s));
   *count = ro.count;
   *n_blocks = ro.n_rows;
-  return MV_OK;
+  if (!seeded) return MV_OK;
+  const mv_status sd = dag_seed_run(ctx, dev, dev.wal.img.as<uint8_t>(), size, ro.rows, ro.blk_status, ro.n_rows, floor_round,
+                                    /*can_grow=*/true, s, seeded);
+  if (sd != MV_OK) (void)hipStreamSynchronize(s);
+  return sd;
+}
+
+mv_status mv_wal_replay(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
+                        uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap, uint64_t* count,
+                        uint64_t* blk_rows, uint8_t* blk_status, uint64_t cap_blocks, uint64_t* n_blocks,
+                        uint64_t* summary, uint64_t* last_seen) {
+  return wal_replay_host(ctx, wal, size, end_pos, map_bits, pos, tag, len, status, cap, count, blk_rows, blk_status,
+                         cap_blocks, n_blocks, summary, last_seen, 0, nullptr);
+}
+
+mv_status mv_wal_recover(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t end_pos, uint32_t map_bits,
+                         uint64_t* pos, uint32_t* tag, uint32_t* len, uint8_t* status, uint64_t cap, uint64_t* count,
+                         uint64_t* blk_rows, uint8_t* blk_status, uint64_t cap_blocks, uint64_t* n_blocks,
+                         uint64_t* summary, uint64_t* last_seen, uint64_t floor_round, uint64_t* seeded) {
+  if (!seeded) return set_err(ctx, MV_E_INVALID_ARG, "bad wal recover args");
+  return wal_replay_host(ctx, wal, size, end_pos, map_bits, pos, tag, len, status, cap, count, blk_rows, blk_status,
+                         cap_blocks, n_blocks, summary, last_seen, floor_round, seeded);
 }
 
 mv_status mv_dev_wal_replay(mv_ctx* ctx, int device, const uint8_t* d_wal, uint64_t size, uint64_t end_pos,

@@ -983,6 +983,177 @@ __global__ void __launch_bounds__(WG) k_dg_keep_inc(DagStore d, DagStore q, uint
   for (uint32_t i = threadIdx.x & 63; i < kc; i += 64) q.inc[to + i] = d.inc[from + i];
 }
 
+// ---------------------------------------------------------------- seeding the DAG store from a replay's rows
+// mv_dev_dag_seed_rows / mv_wal_recover: the rows of mv_wal_replay become stored blocks with records
+// (BlockStore::open with add_unloaded, block_store.rs:50-116, 398-404; the wording of every rule is
+// the header's). The blocks are read in place in the image; a row's offset and length are the
+// caller's, so they are checked against the image before a byte is read, and the include count
+// against the length before it counts. Between the kernels stand the two inserts of the call (the
+// rows' own references towards STORED, the record rows' includes towards WANTED), both by
+// k_ix_claim / fill / settle. The memory model is the one at the top of this file:
+//   k_sd_elig     a lane per row: may it get a record (OK, round >= floor, its bytes fit), its include
+//                 count; the eligible rows and their includes per workgroup (they decide about room)
+//   k_sd_claim    after the own references' insert: a row's slot, and atomicMin of nb0 + row into
+//                 map[slot] -- a record from before the call is below nb0 and stays, otherwise the
+//                 lowest row of a reference wins, as the lowest item owns a slot in k_ix_claim
+//   k_sd_count    first[row] = map[slot] == nb0 + row (what k_sd_claim left), the record rows and
+//                 their includes per workgroup
+//   k_sd_list     a record row writes its record, map[slot] and where its block lies; a first row
+//                 without a record puts map[slot] back to DG_NONE. It reads first[], not map[].
+//   k_sd_inc_src  a wave per record: where its includes lie in the image, for the includes' insert
+//   k_sd_inc      a wave per record: the slots that insert found, in batches of 64
+using mvk::SeedRows;
+constexpr uint8_t SD_ELIGIBLE = 1, SD_MISFIT = 2;
+
+__global__ void __launch_bounds__(WG) k_sd_elig(SeedRows r, uint64_t* __restrict__ wg_a, uint64_t* __restrict__ wg_b,
+                                                u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool el = false, misfit = false;
+  uint64_t k = 0;
+  if (i < r.n) {
+    const uint64_t* row = r.rows + mvk::SD_ROW_WORDS * i;
+    if (r.status[i] == MV_BLOCK_OK) {
+      const uint64_t off = row[1], len = row[2];
+      bool fits = off <= r.size && len <= r.size - off && br::inc_count_readable(len);
+      if (fits) {
+        k = ld64(r.img + off + br::INC_COUNT_OFF);
+        fits = br::includes_inside(len, k) && k <= 0xffffffffull;
+      }
+      misfit = !fits;
+      el = fits && row[4] >= r.floor;
+    }
+    if (!el) k = 0;
+    r.elig[i] = el ? SD_ELIGIBLE : misfit ? SD_MISFIT : 0;
+    r.kc[i] = (uint32_t)k;
+  }
+  uint64_t te, tk;
+  (void)wg_excl(el, &te);
+  (void)wg_excl(k, &tk);
+  if (threadIdx.x == 0) {
+    wg_a[blockIdx.x] = te;
+    wg_b[blockIdx.x] = tk;
+  }
+  wave_count_to(ctl + mvk::IX_CTL_SD_MISFIT, misfit);
+}
+
+__device__ inline bool item_has_slot(u64 it) {
+  const u64 c = code_of(it);
+  return c == C_NEW || c == C_RAISED || c == C_DUP || c == C_NOOP;
+}
+
+__global__ void __launch_bounds__(WG) k_sd_claim(const u64* __restrict__ item, SeedRows r, DagStore d, uint64_t nb0,
+                                                 u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool bad = false;
+  if (i < r.n) {
+    const u64 it = item[i];
+    const uint64_t s = it & SLOT_MASK;
+    bad = !item_has_slot(it) || s >= d.n_slots;
+    r.own_slot[i] = bad ? mvk::IX_NO_SRC : s;
+    if (!bad) atomicMin(d.map + s, (uint32_t)(nb0 + i));
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
+}
+
+__global__ void __launch_bounds__(WG) k_sd_count(SeedRows r, DagStore d, uint64_t nb0, uint64_t* __restrict__ wg_a,
+                                                 uint64_t* __restrict__ wg_b) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  bool rec = false;
+  uint64_t k = 0;
+  if (i < r.n) {
+    const uint64_t s = r.own_slot[i];
+    const bool first = s < d.n_slots && d.map[s] == (uint32_t)(nb0 + i);  // (k_sd_claim's atomics, an earlier kernel)
+    r.first[i] = first;
+    rec = first && r.elig[i] == SD_ELIGIBLE;
+    k = rec ? r.kc[i] : 0;
+  }
+  uint64_t tb, tk;
+  (void)wg_excl(rec, &tb);
+  (void)wg_excl(k, &tk);
+  if (threadIdx.x == 0) {
+    wg_a[blockIdx.x] = tb;
+    wg_b[blockIdx.x] = tk;
+  }
+}
+
+__global__ void __launch_bounds__(WG) k_sd_list(const u64* __restrict__ slots, SeedRows r, DagStore d, uint64_t nb0,
+                                                uint64_t ni0, const uint64_t* __restrict__ base_a,
+                                                const uint64_t* __restrict__ base_b, u64* __restrict__ ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  const bool first = i < r.n && r.first[i];
+  const bool rec = first && r.elig[i] == SD_ELIGIBLE;
+  const uint64_t k = rec ? r.kc[i] : 0;
+  uint64_t tb, tk;
+  const uint64_t rb = nb0 + base_a[blockIdx.x] + wg_excl(rec, &tb);
+  const uint64_t ib = ni0 + base_b[blockIdx.x] + wg_excl(k, &tk);
+  bool bad = false;
+  if (first) {
+    const uint64_t s = r.own_slot[i];  // (below the table's size: k_sd_count checked it)
+    bad = rec && (rb >= d.cap_b || rb - nb0 >= r.n || ib > d.cap_i || k > d.cap_i - ib);
+    if (rec && !bad) {
+      const u64* slot = slots + SLOT_WORDS * s;  // (the key: written by an earlier launch)
+      const u64 a = slot[2], rd = slot[3];
+      d.slot[rb] = s;
+      d.auth[rb] = a < DG_MAX_AUTH ? (uint32_t)a : DG_NONE;
+      d.round[rb] = rd;
+      d.kc[rb] = (uint32_t)k;
+      d.ibase[rb] = ib;
+      d.map[s] = (uint32_t)rb;
+      r.rec_off[rb - nb0] = r.rows[mvk::SD_ROW_WORDS * i + 1];
+      atomicMax(ctl + mvk::IX_CTL_DG_NLO, ~rd);
+      atomicMax(ctl + mvk::IX_CTL_DG_HI, rd);
+    } else {
+      d.map[s] = DG_NONE;  // the claim of a row that gets no record
+    }
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
+}
+
+// where the includes of the call's record `rec` stand among the call's include items; false: out of range
+__device__ inline bool seed_span(const DagStore& d, uint64_t nb0, uint64_t ni0, uint64_t ninc, uint64_t rec, uint64_t* base,
+                                 uint32_t* kc) {
+  const uint64_t ib = d.ibase[nb0 + rec];
+  *kc = d.kc[nb0 + rec];
+  *base = ib - ni0;
+  return ib >= ni0 && ib - ni0 <= ninc && *kc <= ninc - (ib - ni0) && ib <= d.cap_i && *kc <= d.cap_i - ib;
+}
+__global__ void __launch_bounds__(WG) k_sd_inc_src(SeedRows r, DagStore d, uint64_t nb0, uint64_t ni0, uint64_t nrec,
+                                                   uint64_t ninc, uint64_t* __restrict__ inc_src, u64* __restrict__ ctl) {
+  const uint64_t rec = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // a wave per record
+  if (rec >= nrec) return;
+  uint64_t base;
+  uint32_t kc;
+  const bool bad = !seed_span(d, nb0, ni0, ninc, rec, &base, &kc);
+  if (!bad) {
+    const uint64_t off = r.rec_off[rec];  // (k_sd_elig checked off + 64 + 56 kc against the image)
+    for (uint32_t q = threadIdx.x & 63; q < kc; q += 64) inc_src[base + q] = off + br::include_off(q);
+  }
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad && (threadIdx.x & 63) == 0);
+}
+__global__ void __launch_bounds__(WG) k_sd_inc(const u64* __restrict__ item, DagStore d, uint64_t nb0, uint64_t ni0,
+                                               uint64_t nrec, uint64_t ninc, u64* __restrict__ ctl) {
+  const uint64_t rec = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // a wave per record
+  if (rec >= nrec) return;
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t base;
+  uint32_t kc;
+  bool bad = !seed_span(d, nb0, ni0, ninc, rec, &base, &kc);
+  uint64_t nbad = bad && lane == 0;
+  if (!bad) {
+    for (uint32_t q0 = 0; q0 < kc; q0 += 64) {  // bounded by the include count; the wave stays together
+      const uint32_t q = q0 + lane;
+      if (q >= kc) continue;
+      const u64 it = item[base + q];
+      const uint64_t s = it & SLOT_MASK;
+      const bool ok = item_has_slot(it) && s < d.n_slots;
+      d.inc[ni0 + base + q] = ok ? s : DG_NO_SLOT;
+      nbad += !ok;
+    }
+  }
+  nbad = wave_sum64(nbad);
+  if (lane == 0 && nbad) atomicAdd(ctl + mvk::IX_CTL_ERR, (u64)nbad);
+}
+
 // *g = the place of `round` among the call's distinct leader rounds
 __device__ inline bool leader_group(const DecideIn& in, uint64_t round, uint64_t* g) {
   uint64_t lo = 0, hi = in.ng;
@@ -1702,6 +1873,45 @@ hipError_t launch_dag_prune(const DagStore& d, const DagStore& q, uint64_t nb, u
   hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg_b, nwg, base_b, ctl + IX_CTL_DG_NI);
   hipLaunchKernelGGL(k_dg_keep_list, g, b, 0, s, d, q, nb, floor, base_a, base_b, newbase, (u64*)ctl);
   hipLaunchKernelGGL(k_dg_keep_inc, dim3(grid_of(64 * nb)), b, 0, s, d, q, nb, newbase);
+  return hipGetLastError();
+}
+
+hipError_t launch_seed_eligible(const SeedRows& r, uint64_t* wg, uint64_t* ctl, hipStream_t s) {
+  if (r.n == 0) return hipSuccess;
+  const uint64_t nwg = index_groups(r.n);
+  hipLaunchKernelGGL(k_sd_elig, dim3(grid_of(r.n)), dim3(WG), 0, s, r, wg, wg + nwg, (u64*)ctl);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg, nwg, wg + 2 * nwg, ctl + IX_CTL_SD_ELIG);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg + nwg, nwg, wg + 3 * nwg, ctl + IX_CTL_SD_EINC);
+  return hipGetLastError();
+}
+
+hipError_t launch_seed_records(const IndexTable& t, const uint64_t* item, const SeedRows& r, const DagStore& d, uint64_t nb0,
+                               uint64_t ni0, uint64_t* wg, uint64_t* ctl, hipStream_t s) {
+  if (r.n == 0) return hipSuccess;
+  const uint64_t nwg = index_groups(r.n);
+  uint64_t *wg_a = wg, *wg_b = wg + nwg, *base_a = wg + 2 * nwg, *base_b = wg + 3 * nwg;
+  const dim3 g(grid_of(r.n)), b(WG);
+  hipLaunchKernelGGL(k_sd_claim, g, b, 0, s, (const u64*)item, r, d, nb0, (u64*)ctl);
+  hipLaunchKernelGGL(k_sd_count, g, b, 0, s, r, d, nb0, wg_a, wg_b);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg_a, nwg, base_a, ctl + IX_CTL_SD_NREC);
+  hipLaunchKernelGGL(k_ix_scan, dim3(1), dim3(1024), 0, s, wg_b, nwg, base_b, ctl + IX_CTL_SD_NINC);
+  hipLaunchKernelGGL(k_sd_list, g, b, 0, s, (const u64*)t.slots, r, d, nb0, ni0, base_a, base_b, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_seed_inc_src(const SeedRows& r, const DagStore& d, uint64_t nb0, uint64_t ni0, uint64_t nrec, uint64_t ninc,
+                               uint64_t* inc_src, uint64_t* ctl, hipStream_t s) {
+  if (nrec == 0 || ninc == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(inc_src, 0xff, 8 * ninc, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_sd_inc_src, dim3(grid_of(64 * nrec)), dim3(WG), 0, s, r, d, nb0, ni0, nrec, ninc, inc_src, (u64*)ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_seed_inc(const uint64_t* item, const DagStore& d, uint64_t nb0, uint64_t ni0, uint64_t nrec, uint64_t ninc,
+                           uint64_t* ctl, hipStream_t s) {
+  if (nrec == 0 || ninc == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sd_inc, dim3(grid_of(64 * nrec)), dim3(WG), 0, s, (const u64*)item, d, nb0, ni0, nrec, ninc, (u64*)ctl);
   return hipGetLastError();
 }
 

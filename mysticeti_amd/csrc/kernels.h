@@ -574,6 +574,40 @@ hipError_t launch_dag_map(const DagStore& d, uint64_t nb, uint64_t* ctl, hipStre
 hipError_t launch_dag_prune(const DagStore& d, const DagStore& q, uint64_t nb, uint64_t floor, uint64_t* newbase,
                             uint64_t* wg /* 4 x index_groups(nb) */, uint64_t* ctl, hipStream_t s);
 
+// One seed call (mv_dev_dag_seed_rows, mv_wal_recover; kernels: index.hip): the rows of a replay
+// (n x SD_ROW_WORDS words: 1 the offset of the block's bincode in img, 2 its length, 3..8 its
+// reference) with their block verdicts, and the per-row scratch. Offsets and lengths are the
+// caller's: every one is checked against `size` before a byte of img is read.
+constexpr int SD_ROW_WORDS = 10;
+struct SeedRows {
+  const uint8_t* img;
+  uint64_t size;
+  const uint64_t* rows;
+  const uint8_t* status;
+  uint64_t n, floor;
+  uint8_t* elig;       // per row: 0, 1 (may get a record), 2 (MV_BLOCK_OK, but its bytes do not fit the image)
+  uint8_t* first;      // per row: the lowest row of its reference, and that reference had no record
+  uint32_t* kc;        // per row: the include count of an eligible row
+  uint64_t* own_slot;  // per row: the slot of its own reference
+  uint64_t* rec_off;   // per record of the call: where its block lies in img
+};
+// the call's totals stand in words an accept call uses for its own (both zero them first)
+constexpr int IX_CTL_SD_NREC = IX_CTL_NVER, IX_CTL_SD_MISFIT = IX_CTL_NHEADS, IX_CTL_SD_ELIG = IX_CTL_NCAND,
+              IX_CTL_SD_EINC = IX_CTL_NINC, IX_CTL_SD_NINC = IX_CTL_NWANTED;
+// k_sd_elig and its scans: elig, kc; ctl[IX_CTL_SD_ELIG / _EINC] = the eligible rows and their includes,
+// ctl[IX_CTL_SD_MISFIT] += the misfits (wg: 4 x index_groups(n))
+hipError_t launch_seed_eligible(const SeedRows& r, uint64_t* wg, uint64_t* ctl, hipStream_t s);
+// after the own references' insert (item: its records): k_sd_claim, k_sd_count, the scans, k_sd_list.
+// The record rows join d behind its nb0 records and ni0 includes; ctl[IX_CTL_SD_NREC / _NINC] = how many.
+hipError_t launch_seed_records(const IndexTable& t, const uint64_t* item, const SeedRows& r, const DagStore& d, uint64_t nb0,
+                               uint64_t ni0, uint64_t* wg /* 4 x index_groups(n) */, uint64_t* ctl, hipStream_t s);
+// inc_src[j] = where include item j of the call's nrec records lies in img (IX_NO_SRC for none)
+hipError_t launch_seed_inc_src(const SeedRows& r, const DagStore& d, uint64_t nb0, uint64_t ni0, uint64_t nrec, uint64_t ninc,
+                               uint64_t* inc_src, uint64_t* ctl, hipStream_t s);
+// after the includes' insert (item: its records): their slots into the records
+hipError_t launch_seed_inc(const uint64_t* item, const DagStore& d, uint64_t nb0, uint64_t ni0, uint64_t nrec, uint64_t ninc,
+                           uint64_t* ctl, hipStream_t s);
+
 // One decide call over n leader rows sorted by round: the distinct rounds (ng of them), where each
 // round's rows start (ng + 1 words), and per sorted row its authority, round and place in the
 // caller's arrays. gmax: the most rows of one round.

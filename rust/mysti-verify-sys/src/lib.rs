@@ -119,6 +119,11 @@ extern "C" {
                          pos: *mut u64, tag: *mut u32, len: *mut u32, status: *mut u8, cap: u64,
                          count: *mut u64, blk_rows: *mut u64, blk_status: *mut u8, cap_blocks: u64,
                          n_blocks: *mut u64, summary: *mut u64, last_seen: *mut u64) -> i32;
+    pub fn mv_wal_recover(ctx: *mut mv_ctx, wal: *const u8, size: u64, end_pos: u64, map_bits: u32,
+                          pos: *mut u64, tag: *mut u32, len: *mut u32, status: *mut u8, cap: u64,
+                          count: *mut u64, blk_rows: *mut u64, blk_status: *mut u8, cap_blocks: u64,
+                          n_blocks: *mut u64, summary: *mut u64, last_seen: *mut u64, floor_round: u64,
+                          seeded: *mut u64) -> i32;
     pub fn mv_wal_layout(payload_len: *const u64, n: u64, map_bits: u32, start: u64, pos: *mut u64) -> u64;
     pub fn mv_frame_blocks(buf: *const u8, len: u64, off: *mut u64, blen: *mut u64, cap: u64,
                            consumed: *mut u64) -> i64;
@@ -166,6 +171,9 @@ extern "C" {
                                  d_info: *mut u64, n_sequence: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_dev_index_insert(ctx: *mut mv_ctx, device: i32, d_words: *const u64, stride_words: u64, n: u64,
                                state: u32, stream: *mut c_void) -> i32;
+    pub fn mv_dev_dag_seed_rows(ctx: *mut mv_ctx, device: i32, d_wal: *const u8, size: u64, d_blk_rows: *const u64,
+                                d_blk_status: *const u8, n_rows: u64, floor_round: u64, seeded: *mut u64,
+                                stream: *mut c_void) -> i32;
     pub fn mv_dev_verify_frames(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,
                                 d_soff: *const u64, d_slen: *const u64, ns: u32, d_consumed: *mut u64,
                                 d_drop_msg: *mut u32, d_msgs: *mut u32, cap_msgs: u64, n_msgs: *mut u64,

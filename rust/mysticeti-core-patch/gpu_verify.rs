@@ -166,6 +166,44 @@ impl GpuVerifier {
         Ok(out)
     }
 
+    /// `wal_replay`, then the replayed blocks become stored blocks with records in the DAG store
+    /// (mv_wal_recover: BlockStore::open with add_unloaded, block_store.rs:398-404, as what makes a
+    /// replayed block visible to BaseCommitter). Needs `dag_reserve`. `floor_round`: rows of lower
+    /// rounds get no record, as after `dag_prune`. The five words: the references raised to
+    /// MV_REF_STORED, the records appended and their includes, the includes no row of the WAL holds
+    /// (0 for a WAL this node wrote), and verified rows whose bytes did not fit the image.
+    pub fn wal_recover(&self, wal: &[u8], end_pos: u64, map_bits: u32, committee_size: usize,
+                       floor_round: u64) -> eyre::Result<(WalReplay, [u64; 5])> {
+        let cap = wal.len() / 16 + 1;
+        let mut out = WalReplay {
+            pos: vec![0; cap],
+            tag: vec![0; cap],
+            len: vec![0; cap],
+            status: vec![0; cap],
+            rows: vec![0; 10 * cap],
+            blk_status: vec![0; cap],
+            summary: [0; 3],
+            last_seen: vec![0; committee_size],
+        };
+        let (mut count, mut n_blocks, mut seeded) = (0u64, 0u64, [0u64; 5]);
+        let rc = unsafe {
+            sys::mv_wal_recover(self.ctx, wal.as_ptr(), wal.len() as u64, end_pos, map_bits, out.pos.as_mut_ptr(),
+                                out.tag.as_mut_ptr(), out.len.as_mut_ptr(), out.status.as_mut_ptr(), cap as u64,
+                                &mut count, out.rows.as_mut_ptr(), out.blk_status.as_mut_ptr(), cap as u64,
+                                &mut n_blocks, out.summary.as_mut_ptr(), out.last_seen.as_mut_ptr(), floor_round,
+                                seeded.as_mut_ptr())
+        };
+        ensure!(rc == sys::MV_OK, "mv_wal_recover: {}", self.last_error());
+        let (n, b) = (count as usize, n_blocks as usize);
+        out.pos.truncate(n);
+        out.tag.truncate(n);
+        out.len.truncate(n);
+        out.status.truncate(n);
+        out.rows.truncate(10 * b);
+        out.blk_status.truncate(b);
+        Ok((out, seeded))
+    }
+
     /// Seeds the index of block references with references the store holds (MV_REF_HAVE): the
     /// genesis references, and after a replay the rows' words 3..8 (BlockStore::open's
     /// add_unloaded, block_store.rs:398-404). `refs` holds six words per reference: authority,
