@@ -61,6 +61,10 @@
  *                          every add_blocks
  *   mv_commit_leaders      try_commit itself: the direct rule, try_indirect_decide (:294-318) over
  *                          BlockStore::linked_to_round (block_store.rs:306-327), and the decided prefix
+ *   mv_seal_blocks         StatementBlock::new_with_signer (types.rs:155-218) on blocks that are bincode
+ *                          already: Signer::sign_block (crypto.rs:199-223) over the digest of the signed
+ *                          pre-image (crypto.rs:85-128) and BlockDigest::new (crypto.rs:38-61), written
+ *                          into the block's own bytes; with MV_SEAL_LINK a whole DAG, round by round
  *
  * Conventions
  *   - The caller owns every buffer passed in and out; they must stay valid for the call.
@@ -659,6 +663,56 @@ mv_status mv_wal_recover(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_
                          uint64_t cap_blocks, uint64_t* n_blocks, uint64_t* summary /* 3 */,
                          uint64_t* last_seen /* committee size */, uint64_t floor_round, uint64_t* seeded /* 5 */);
 
+/* ---- sealing blocks ----
+ * The inverse of mv_verify_blocks: StatementBlock::new_with_signer (types.rs:155-218), i.e.
+ * Signer::sign_block (crypto.rs:199-223) and BlockDigest::new (crypto.rs:38-61), for n blocks that
+ * are Data<StatementBlock> bincode already (types.rs:93-114, data.rs:43-52) but for their digest
+ * and signature fields, which are placeholders: read by nobody, overwritten. */
+#define MV_SEAL_OK 0             /* sealed */
+#define MV_SEAL_PARSE_ERROR 1    /* fails what MV_BLOCK_PARSE_ERROR fails; bytes untouched */
+#define MV_SEAL_UNKNOWN_AUTHOR 2 /* parses, authority >= n_auth; bytes untouched */
+#define MV_SEAL_UNLINKED 3       /* MV_SEAL_LINK: an include names a block of this call of the same or a
+                                    later round; bytes untouched */
+#define MV_SEAL_LINK 1u          /* flags: the blocks are a DAG, see below */
+/* For every block buf[off[i], off[i] + len[i]) that deserializes and whose authority < n_auth:
+ *   m   = Blake2b-256 of the signed pre-image (BlockDigest::digest_without_signature,
+ *         crypto.rs:85-128: what mv_block_preimage returns; neither the block's own digest nor its
+ *         signature is part of it)
+ *   sig = the RFC 8032 signature of m under seeds[authority] (Signer::sign_block, crypto.rs:199-223;
+ *         what mv_ed25519_sign gives for that seed and m)
+ *   d   = Blake2b-256(pre-image || sig) (BlockDigest::new, crypto.rs:38-61)
+ * sig goes to the 64 signature bytes the bincode ends on and d to bytes 24..56 of the block (the
+ * digest of its own BlockReference, the layout block_codec.h names). No other byte of buf changes,
+ * between and after blocks included. Blocks must not overlap. status[i] = MV_SEAL_*; msg_digest[i]
+ * = m and block_digest[i] = d (either array may be NULL), zero for a block that was not sealed.
+ * A round-0 block is sealed like any other: the reference's genesis blocks carry a zero signature
+ * (types.rs:141-150) and stay with the caller.
+ *
+ * flags & MV_SEAL_LINK seals a DAG in one call. The blocks that parse (known authority or not) must
+ * stand in non-decreasing round order, else MV_E_INVALID_ARG with nothing written. The call keeps a
+ * table (authority, round) -> block over its blocks that are neither parse errors nor of an unknown
+ * author; of several blocks with one key the lowest index holds it. Before block i is hashed,
+ * every include whose (authority, round) is a key of the table
+ *   - of a round below block i's: gets the digest the call computed for that block written over
+ *     its 32 digest bytes -- unless that block was itself left MV_SEAL_UNLINKED, which has no
+ *     fresh digest: the include then keeps its bytes;
+ *   - of block i's round or a later one: is not linked. Block i is MV_SEAL_UNLINKED and no byte
+ *     of it changes (StatementBlock::verify would reject it as MV_BLOCK_INCLUDE_ROUND anyway).
+ * Includes that match no key keep their bytes: genesis, and blocks sealed earlier. One device
+ * step runs per distinct round, lowest first; the host reads the blocks' (authority, round) back
+ * once per call, and from them checks the order, fills the table (an open-addressed hash whose
+ * longest probe bounds every device lookup) and cuts the steps. Without the flag there is neither
+ * table nor order: every block is sealed on its own, in one step.
+ * n_auth <= 2^20; seeds may be NULL when n_auth is 0 (every block is then MV_SEAL_UNKNOWN_AUTHOR).
+ * No committee is needed. Runs on the context's first device; takes the context in turn.
+ * The seeds are secrets: the library's device copies of them and of the expanded keys (scalar and
+ * prefix) are zeroed before the call returns; the host-buffer call reads `seeds` from the
+ * caller's memory as it is (pageable or pinned), like mv_ed25519_sign. */
+mv_status mv_seal_blocks(mv_ctx* ctx, uint8_t* buf, const uint64_t* off, const uint64_t* len, uint32_t n,
+                         const uint8_t* seeds /* n_auth x 32 */, uint32_t n_auth, uint32_t flags,
+                         uint8_t* status /* n, MV_SEAL_* */, uint8_t* msg_digest /* n x 32 or NULL */,
+                         uint8_t* block_digest /* n x 32 or NULL */);
+
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
  * library's stream for that device). They enqueue work and return without synchronising. */
@@ -775,6 +829,19 @@ mv_status mv_dev_decide_leaders(mv_ctx* ctx, int device, const uint64_t* d_leade
  * *n_sequence on the host. The rows are read back to be checked and grouped; `stream` is synchronised. */
 mv_status mv_dev_commit_leaders(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_out,
                                 uint64_t* d_info, uint64_t* n_sequence, void* stream);
+/* mv_seal_blocks on blocks already in HBM (new_with_signer as there: types.rs:155-218,
+ * crypto.rs:38-61, 199-223): the image is patched in place. Every array is device memory; d_buf is
+ * 8-byte aligned with 16 readable bytes past buf_bytes, d_seeds 4-byte and the digest arrays (n x 32,
+ * may be NULL) 8-byte aligned. A block whose span leaves buf_bytes is MV_SEAL_PARSE_ERROR.
+ * Synchronises `stream` (the call's scratch -- expanded keys, zeroed again before it returns, heads,
+ * table -- is the context's, and
+ * under MV_SEAL_LINK the order check, the table and the steps come from the heads read back).
+ * MV_E_INVALID_ARG for rounds out of order leaves d_buf as it was and d_status holding the first
+ * pass's verdicts. The context's first device only. */
+mv_status mv_dev_seal_blocks(mv_ctx* ctx, int device, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_off,
+                             const uint64_t* d_len, uint32_t n, const uint8_t* d_seeds, uint32_t n_auth,
+                             uint32_t flags, uint8_t* d_status, uint8_t* d_msg_digest, uint8_t* d_block_digest,
+                             void* stream);
 /* crc32fast::hash of n strings of device buffer d_buf at d_off/d_len (device arrays) -> d_out. Enqueue only. */
 mv_status mv_dev_crc32(mv_ctx* ctx, int device, const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len,
                        uint32_t n, uint32_t* d_out, void* stream);

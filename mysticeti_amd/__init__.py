@@ -80,8 +80,13 @@ EXPORTS = [
     "mv_index_insert_stored", "mv_connect_blocks", "mv_dev_connect_blocks", "mv_pending_reserve", "mv_pending_stats",
     "mv_dag_reserve", "mv_dag_prune", "mv_dag_stats", "mv_decide_leaders", "mv_dev_decide_leaders",
     "mv_commit_leaders", "mv_dev_commit_leaders", "mv_wal_recover", "mv_dev_dag_seed_rows",
+    "mv_seal_blocks", "mv_dev_seal_blocks",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
+# per-block outcomes of mv_seal_blocks, and its flag
+SEAL_STATUS = ["OK", "PARSE_ERROR", "UNKNOWN_AUTHOR", "UNLINKED"]
+SEAL_OK, SEAL_PARSE_ERROR, SEAL_UNKNOWN_AUTHOR, SEAL_UNLINKED = range(4)
+SEAL_LINK = 1
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
 # ... and of the replay loop of BlockStore::open (mv_wal_replay only)
 WAL_UNKNOWN_TAG, WAL_BLOCK_DECODE, WAL_UNKNOWN_AUTHORITY = 4, 5, 6
@@ -167,6 +172,8 @@ def load_library(path: str = LIB_PATH):
     lib.mv_stage_times.argtypes = [vp, vp, vp, ctypes.c_int]
     lib.mv_dev_verify_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, vp, vp, vp, vp]
     lib.mv_dev_ed25519_sign.argtypes = [vp, ctypes.c_int, vp, vp, u32, vp, vp, vp]
+    lib.mv_seal_blocks.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
+    lib.mv_dev_seal_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp]
     lib.mv_selftest.argtypes = [vp, ctypes.c_int, vp, u32, vp]
     lib.mv_selftest_batch_prep.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     lib.mv_selftest_batch_msm.argtypes = [vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]
@@ -383,6 +390,40 @@ class Engine:
         self._check(self.lib.mv_verify_blocks(self.ctx, _p(buf), _p(offs), _p(lens), n, _p(st), _p(md), _p(bd)),
                     "mv_verify_blocks")
         return st, md, bd
+
+    def seal_blocks(self, buf: np.ndarray, offs, lens, seeds, link: bool = False):
+        """StatementBlock::new_with_signer on bincode blocks whose digest and signature fields are
+        placeholders (mv_seal_blocks): `buf` (a writable uint8 array) is patched in place with each
+        block's signature under seeds[authority] and its digest; link=True also writes the fresh
+        digests into the includes that name blocks of the call, round by round. Returns
+        (status MV_SEAL_*, msg_digest, block_digest)."""
+        if not (isinstance(buf, np.ndarray) and buf.dtype == np.uint8 and buf.flags.c_contiguous and
+                buf.flags.writeable):
+            raise ValueError("seal_blocks patches buf in place: a writable contiguous uint8 array")
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        n = offs.shape[0]
+        if n and int((offs + lens).max()) > buf.shape[0]:
+            raise ValueError("a block reaches past the buffer")
+        seeds = _u8(seeds, 32)
+        st = np.zeros(n, dtype=np.uint8)
+        md = np.zeros((n, 32), dtype=np.uint8)
+        bd = np.zeros((n, 32), dtype=np.uint8)
+        self._check(self.lib.mv_seal_blocks(self.ctx, _p(buf), _p(offs), _p(lens), n, _p(seeds), seeds.shape[0],
+                                            SEAL_LINK if link else 0, _p(st), _p(md), _p(bd)), "mv_seal_blocks")
+        return st, md, bd
+
+    def dev_seal_blocks(self, device: int, d_buf, buf_bytes: int, d_off, d_len, d_seeds, d_status, d_md=None,
+                        d_bd=None, link: bool = False, stream_handle: int = 0):
+        """mv_seal_blocks on HBM-resident bincode (torch uint8 buffer padded by 16 bytes, int64
+        offsets and lengths, uint8 seeds [n_auth, 32]): the image is patched in place.
+        Synchronises the stream."""
+        vp = ctypes.c_void_p
+        self._check(self.lib.mv_dev_seal_blocks(
+            self.ctx, device, vp(d_buf.data_ptr()), int(buf_bytes), vp(d_off.data_ptr()), vp(d_len.data_ptr()),
+            d_off.shape[0], vp(d_seeds.data_ptr()), d_seeds.shape[0], SEAL_LINK if link else 0,
+            vp(d_status.data_ptr()), vp(d_md.data_ptr()) if d_md is not None else None,
+            vp(d_bd.data_ptr()) if d_bd is not None else None, vp(stream_handle or None)), "mv_dev_seal_blocks")
 
     def verify_frames(self, buf):
         """Blocks of received NetworkMessage frames (network.rs:400-447) verified in place:

@@ -110,6 +110,40 @@ def build_rounds(engine, rounds: int, n_auth: int, seeds: Sequence[bytes], n_inc
     return out
 
 
+def build_rounds_sealed(engine, rounds: int, n_auth: int, seeds: Sequence[bytes], n_inc: int, n_vr: int,
+                        with_tx: bool, epoch: int = 0) -> List[bytes]:
+    """build_rounds' DAG with the host out of the per-round loop: every round is encoded once with
+    zero digests and signatures (the includes carry authority and round only), and one
+    Engine.seal_blocks(link=True) call signs, digests and links all of them on the GPU
+    (StatementBlock::new_with_signer, types.rs:155-218). Without VoteRanges (config 1) the result is
+    build_rounds' byte for byte. The link rule covers includes, not the references inside
+    statements, so the VoteRanges here name genesis blocks, whose digests are known up front, where
+    build_rounds' name blocks of the round before: same sizes, same verdicts, other bytes."""
+    gen = genesis_refs(n_auth, epoch)
+    zero = bytes(32)
+    out: List[bytes] = []
+    for r in range(1, rounds + 1):
+        prev = gen if r == 1 else [(a, r - 1, zero) for a in range(n_auth)]
+        for a in range(n_auth):
+            others = [x for x in range(n_auth) if x != a]
+            inc = [prev[a]] + [prev[x] for x in others[: n_inc - 1]]
+            shares = [config4_tx(r, a)] if with_tx else []
+            ranges = [(gen[(a + 1 + v) % n_auth], 0, 1 + (v % 7)) for v in range(n_vr)]
+            bn, _ = encode(a, r, inc, shares, ranges, r * 10**8 + a, epoch, bytes(64), zero)
+            out.append(bn)
+    lens = np.array([len(b) for b in out], dtype=np.uint64)
+    offs = np.zeros(len(out), dtype=np.uint64)
+    if len(out) > 1:
+        offs[1:] = np.cumsum(lens)[:-1]
+    buf = np.frombuffer(bytearray(b"".join(out)), dtype=np.uint8)
+    st, _, _ = engine.seal_blocks(buf, offs, lens, np.frombuffer(b"".join(seeds), dtype=np.uint8).reshape(n_auth, 32),
+                                  link=True)
+    if st.any():
+        raise RuntimeError(f"seal_blocks left {int(np.count_nonzero(st))} blocks unsealed")
+    raw = buf.tobytes()
+    return [raw[int(o): int(o) + int(l)] for o, l in zip(offs, lens)]
+
+
 def config1(engine, rounds: int) -> List[bytes]:
     """Config 1: 4 authorities, all with the zero seed (dummy_signer, crypto.rs:355-357)."""
     return build_rounds(engine, rounds, 4, [bytes(32)] * 4, n_inc=4, n_vr=0, with_tx=False)

@@ -784,6 +784,7 @@ void mv_destroy(mv_ctx* ctx) {
     mvr::reset(dev.wal);
     mvr::reset(dev.frm);
     mvr::reset(dev.index);
+    mvr::reset(dev.seal);
     watch.phase("frees: batch and single path");
     mvr::reset(dev.batch);
     mvr::reset(dev.single);

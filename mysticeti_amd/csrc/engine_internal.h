@@ -1,7 +1,7 @@
 // What the engine's source files share (host only): the per-device state and the context, the
 // error plumbing, the sharding helpers, and the declarations of the functions that cross files
 // (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp,
-// engine_index.cpp).
+// engine_index.cpp, engine_seal.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -205,6 +205,13 @@ struct Device {
       DevBuf src, newbase, lead, state, lists, sup, res, cmask, cm, marks, span;
     } dag;
   } index;
+
+  // mv_seal_blocks (seal.hip): the expanded keys, the scan's heads, the link table, both digest
+  // arrays, and the bytes, off | len, status and seeds of host-buffer calls (calls are synchronous)
+  struct Seal {
+    DevBuf keys, heads, tab, md, bd, in, ol, st, seeds;
+    HostBuf h;
+  } seal;
 
   // the resident online service (k_online) of this device, made on first use
   std::shared_ptr<OnlineSvc> online;

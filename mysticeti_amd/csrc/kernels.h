@@ -678,4 +678,35 @@ hipError_t launch_commit_resolve(const IndexTable& t, const DagStore& d, uint64_
                                  uint64_t* out, uint64_t* info, uint64_t* ctl, hipStream_t s);
 // ctl[IX_CTL_CM_NSEQ] = the rows of the longest prefix of COMMIT / SKIP rows among those of round > 0
 hipError_t launch_commit_prefix(const DecideIn& in, const uint64_t* out, uint64_t* ctl, hipStream_t s);
+
+// seal.hip: mv_seal_blocks (StatementBlock::new_with_signer on bincode blocks with placeholder
+// digest and signature fields). keys: 24 words per authority (a mod l, prefix, public key).
+hipError_t launch_seal_keys(const uint8_t* seeds, uint32_t n_auth, const void* btab, uint32_t* keys, hipStream_t s);
+// the walk alone: status[i] = MV_SEAL_OK / PARSE_ERROR / UNKNOWN_AUTHOR, heads[2 i] = authority,
+// heads[2 i + 1] = round (both all ones for a parse error)
+hipError_t launch_seal_scan(const uint8_t* buf, uint64_t buf_bytes, const uint64_t* off, const uint64_t* len,
+                            uint32_t n, uint32_t n_auth, uint8_t* status, uint64_t* heads, hipStream_t s);
+// The (authority, round) -> block table of a linked call, built on the host: slots of four words
+// (round low, round high, authority, block; block = all ones: empty), mask + 1 of them (a power
+// of two), linear probing from seal_table_hash & mask, no key further than max_probe slots from
+// there. slots == nullptr: an unlinked call.
+struct SealTable {
+  const void* slots;
+  uint32_t mask, max_probe;
+};
+__host__ __device__ inline uint32_t seal_table_hash(uint64_t a, uint64_t r) {
+  uint64_t x = (r * 0x9E3779B97F4A7C15ull) ^ (a * 0xC2B2AE3D27D4EB4Full);
+  x ^= x >> 29;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 32;
+  return (uint32_t)x;
+}
+// a step of at least this many blocks runs four waves per workgroup on one LDS copy of the
+// fixed-base table (the throughput shape); smaller steps one wave per workgroup
+constexpr uint32_t SEAL_THROUGHPUT_MIN = 1u << 15;
+// blocks [lo, hi) whose status is MV_SEAL_OK: linked (with a table), hashed, signed, patched in
+// place; md / bd: n x 32 bytes, 8-byte aligned, bd read by later levels
+hipError_t launch_seal_level(uint8_t* buf, uint64_t buf_bytes, const uint64_t* off, const uint64_t* len, uint32_t lo,
+                             uint32_t hi, const uint32_t* keys, const void* btab, const SealTable& t, uint8_t* status,
+                             uint8_t* md, uint8_t* bd, hipStream_t s);
 }  // namespace mvk

@@ -67,6 +67,12 @@ pub const MV_BLOCK_THRESHOLD_CLOCK: u8 = 10;
 pub const MV_BLOCK_VOTE_RANGE_TOO_LONG: u8 = 11;
 pub const MV_BLOCK_VOTE_RANGE_END_TOO_LARGE: u8 = 12;
 
+pub const MV_SEAL_OK: u8 = 0;
+pub const MV_SEAL_PARSE_ERROR: u8 = 1;
+pub const MV_SEAL_UNKNOWN_AUTHOR: u8 = 2;
+pub const MV_SEAL_UNLINKED: u8 = 3;
+pub const MV_SEAL_LINK: u32 = 1;
+
 pub const MV_WAL_OK: u8 = 0;
 pub const MV_WAL_CRC_MISMATCH: u8 = 1;
 pub const MV_WAL_NONZERO_CRC_LEN0: u8 = 2;
@@ -174,6 +180,13 @@ extern "C" {
     pub fn mv_dev_dag_seed_rows(ctx: *mut mv_ctx, device: i32, d_wal: *const u8, size: u64, d_blk_rows: *const u64,
                                 d_blk_status: *const u8, n_rows: u64, floor_round: u64, seeded: *mut u64,
                                 stream: *mut c_void) -> i32;
+    pub fn mv_seal_blocks(ctx: *mut mv_ctx, buf: *mut u8, off: *const u64, len: *const u64, n: u32,
+                          seeds: *const u8, n_auth: u32, flags: u32, status: *mut u8, msg_digest: *mut u8,
+                          block_digest: *mut u8) -> i32;
+    pub fn mv_dev_seal_blocks(ctx: *mut mv_ctx, device: i32, d_buf: *mut u8, buf_bytes: u64, d_off: *const u64,
+                              d_len: *const u64, n: u32, d_seeds: *const u8, n_auth: u32, flags: u32,
+                              d_status: *mut u8, d_msg_digest: *mut u8, d_block_digest: *mut u8,
+                              stream: *mut c_void) -> i32;
     pub fn mv_dev_verify_frames(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,
                                 d_soff: *const u64, d_slen: *const u64, ns: u32, d_consumed: *mut u64,
                                 d_drop_msg: *mut u32, d_msgs: *mut u32, cap_msgs: u64, n_msgs: *mut u64,
