@@ -1,5 +1,5 @@
 // Where a block's own BlockReference and its includes lie in bincode(Data<StatementBlock>), and
-// what must hold before each load: stated once for the index kernels (index.hip) and the host
+// what must hold before each load: stated once for the index kernels (index.hip, dag_store.hip) and the host
 // side of mv_accept_blocks (engine_index.cpp).
 //
 //   own reference   bytes 0..56: authority u64, round u64, digest length u64 (32), 32 digest

@@ -1,7 +1,7 @@
 // What the engine's source files share (host only): the per-device state and the context, the
 // error plumbing, the sharding helpers, and the declarations of the functions that cross files
 // (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp,
-// engine_index.cpp, engine_seal.cpp).
+// engine_index.cpp, engine_connect.cpp, engine_dag.cpp, engine_decide.cpp, engine_seal.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -165,7 +165,7 @@ struct Device {
     DevBuf s, f, o, in, tab;
   } frm;
 
-  // the index of block references (index.hip, engine_index.cpp), made on first use: the table
+  // the index of block references (index.hip, engine_index.cpp and the files beside them), made on first use: the table
   // and its control words, and the scratch of insert, lookup, list and accept calls
   struct Index {
     DevBuf tab, ctl;
@@ -232,7 +232,7 @@ struct mv_ctx {
   uint32_t max_batch = 1u << 20;
   uint32_t flags = 0;
   uint32_t secret[8] = {0};         // batch-path z_i PRF key (from /dev/urandom)
-  uint64_t index_secret[2] = {0};   // the index's hash key (index.hip), drawn with it
+  uint64_t index_secret[2] = {0};   // the index's hash key (index_dev.h), drawn with it
   std::atomic<uint64_t> calls{0};   // batch calls, the PRF's per-call input
   std::atomic<uint64_t> batches{0}, fallbacks{0}, groups_run{0}, groups_failed{0};
   // sub-batch equations per batch: groups_fixed != 0 forces that many; 0 = adaptive:
@@ -465,8 +465,44 @@ mv_status enqueue_blocks(mv_ctx* ctx, Device& dev, const uint8_t* d_buf, uint64_
                          hipStream_t s, DevBuf* own = nullptr, Device::BlkAux* own_aux = nullptr);
 std::vector<uint64_t> balanced_cuts(const uint64_t* w, uint64_t n, uint32_t parts);
 
-// engine_index.cpp: one seed call (mv_dev_dag_seed_rows) on stream s, which it synchronises; the image, the
-// rows and their block verdicts are device memory, seeded (5 words) is the host's
+// engine_index.cpp: the table and the accept call, which the three files below build on (each
+// function is described where it is defined)
+constexpr size_t ix_al(size_t x) { return (x + 255) & ~(size_t)255; }
+using Index = Device::Index;
+using Pending = Device::Index::Pending;
+using Dag = Device::Index::Dag;
+mvk::IndexTable table_of(mv_ctx* ctx, const Index& ix);
+mv_status index_dev(mv_ctx* ctx, Device*& dev);
+mv_status index_ctl(mv_ctx* ctx, Device& dev, hipStream_t s);
+mv_status read_ctl(mv_ctx* ctx, Device& dev, hipStream_t s, const uint64_t** words);
+mv_status order_behind_ahead(mv_ctx* ctx, Device& dev, hipStream_t s);
+mv_status index_room_for_more(mv_ctx* ctx, Device& dev, uint64_t more, bool can_grow, hipStream_t s);
+mv_status insert_rounds(mv_ctx* ctx, Device& dev, const mvk::IndexKeys& ks, uint64_t n, uint32_t state, hipStream_t s);
+// Where accept_run leaves its results (device memory of dev.index)
+struct AcceptOut {
+  uint64_t n_missing = 0;
+  const uint8_t *status = nullptr, *state = nullptr;
+  const uint64_t* missing = nullptr;
+  // for the connect call: the call's arrays, the candidates (their slots are in pend.cand_slot) and
+  // their includes (whose insert's records are in index.item)
+  mvk::AcceptArrays a{};
+  uint64_t ncand = 0, ninc = 0;
+};
+mv_status accept_run(mv_ctx* ctx, Device& dev, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_off,
+                     const uint64_t* d_len, const uint64_t* d_grp, uint32_t n32, uint64_t cap_missing, bool can_grow,
+                     hipStream_t s, AcceptOut& out, bool connect = false);
+mv_status stage_blocks(mv_ctx* ctx, Device& dev, const uint8_t* buf, const uint64_t* off, const uint64_t* len,
+                       const uint64_t* grp, uint32_t n, uint64_t cap_missing, hipStream_t s, AcceptOut& ao, bool connect);
+
+// engine_connect.cpp: the suspended-block store
+mvk::PendStore pend_view(const Pending& pd, int k);
+mv_status pending_room(mv_ctx* ctx, Device& dev, uint64_t more_b, uint64_t more_i, bool can_grow, hipStream_t s);
+
+// engine_dag.cpp: the DAG store; one seed call (mv_dev_dag_seed_rows) on stream s, which it synchronises; the image,
+// the rows and their block verdicts are device memory, seeded (5 words) is the host's
+mvk::DagStore dag_view(const Dag& dg, const DevBuf& rec, const DevBuf& inc, uint64_t cap_b, uint64_t cap_i);
+mvk::DagStore dag_view(const Dag& dg);
+mv_status dag_room(mv_ctx* ctx, Device& dev, uint64_t more_b, uint64_t more_i, hipStream_t s, bool can_grow = true);
 mv_status dag_seed_run(mv_ctx* ctx, Device& dev, const uint8_t* d_img, uint64_t size, const uint64_t* d_rows,
                        const uint8_t* d_status, uint64_t n, uint64_t floor_round, bool can_grow, hipStream_t s,
                        uint64_t* seeded);

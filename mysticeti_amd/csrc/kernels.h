@@ -424,7 +424,7 @@ hipError_t launch_frame_verdicts(uint32_t* rows, uint64_t n_rows, const uint8_t*
                                  uint32_t ns, const uint32_t* kept, const uint32_t* row_base, uint32_t* drop_msg,
                                  hipStream_t s);
 // index.hip: the index of block references and the accept call (rules: block_ref.h; the table, the
-// insert protocol and its memory model are described at the top of index.hip).
+// insert protocol and the memory model of all index kernels are described at the top of index_dev.h).
 struct IndexTable {
   unsigned long long* slots;  // mask + 1 slots of 8 words (null: no table yet, every lookup is ABSENT)
   uint64_t mask;
@@ -462,8 +462,23 @@ constexpr int IX_CTL_HAVE = 0, IX_CTL_WANTED = 1, IX_CTL_MAXPROBE = 2, IX_CTL_RE
               IX_CTL_CM_MOVED = IX_CTL_DG_NI + 11, IX_CTL_CM_NSEQ = IX_CTL_DG_NI + 12,
               IX_CTL_CM_NSPAN = IX_CTL_DG_NI + 13,  // the records of the rounds a commit call's levels read
               IX_CTL_WORDS = IX_CTL_DG_NI + 16;
-uint64_t index_groups(uint64_t n);  // workgroups of the per-item kernels: wgcount / wgbase hold one word each
-hipError_t launch_index_scan(const uint64_t* wgcount, uint64_t nwg, uint64_t* wgbase, uint64_t* total, hipStream_t s);
+constexpr int IX_WG = 256;  // lanes (items) per workgroup of the per-item kernels
+inline uint64_t index_groups(uint64_t n) { return (n + IX_WG - 1) / IX_WG; }
+// The per-workgroup scratch of a count / scan / list pass over n items: two counts per workgroup and
+// their scans, index_groups(n) words each. The host sizes the buffer and the launchers carve it here.
+struct WgScan {
+  uint64_t *count_a, *count_b, *base_a, *base_b;
+};
+inline size_t wg_scan_bytes(uint64_t n) { return 4 * 8 * (size_t)index_groups(n); }
+inline WgScan wg_scan_of(void* p, uint64_t n) {
+  uint64_t* w = (uint64_t*)p;
+  const uint64_t g = index_groups(n);
+  return WgScan{w, w + g, w + 2 * g, w + 3 * g};
+}
+// wgbase[g] = the counts of the nwg workgroups before g, *total = all of them. With `running` (may
+// be null) the bases stand behind *running, which then grows by the total.
+hipError_t launch_index_scan(const uint64_t* wgcount, uint64_t nwg, uint64_t* wgbase, uint64_t* total, uint64_t* running,
+                             hipStream_t s);
 // one insert round (k_ix_claim, k_ix_fill, k_ix_settle) of n items towards `state`; item: n words
 // of per-item records, kept between rounds; round > 0 takes the items the last round left over
 // (ctl[IX_CTL_RETRY], zeroed by the caller before each round)
@@ -477,9 +492,10 @@ hipError_t launch_index_lookup(const IndexTable& t, const IndexKeys& ks, uint64_
 // every entry of the old table into t (empty, zeroed)
 hipError_t launch_index_rebuild(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* ctl,
                                 hipStream_t s);
-// count / scan / list of the WANTED entries: *total, the first cap into out (cap x 6 words)
-hipError_t launch_index_wanted(const IndexTable& t, uint64_t* wgcount, uint64_t* wgbase, uint64_t* total, uint64_t* out,
-                               uint64_t cap, hipStream_t s);
+// count / scan / list of the WANTED entries: *total, the first cap into out (cap x 6 words);
+// wg: wg_scan_bytes(slots), as for every launcher below that takes one (of its own item count)
+hipError_t launch_index_wanted(const IndexTable& t, uint64_t* wg, uint64_t* total, uint64_t* out, uint64_t cap,
+                               hipStream_t s);
 struct AcceptArrays {  // one accept call: the caller's blocks and the per-block / per-workgroup scratch
   const uint8_t* buf;
   uint64_t buf_bytes;
@@ -508,10 +524,10 @@ hipError_t launch_accept_probe(const IndexTable& t, const AcceptArrays& a, uint6
 hipError_t launch_accept_groups(const AcceptArrays& a, uint64_t* ctl, hipStream_t s);
 hipError_t launch_accept_own_states(const AcceptArrays& a, const uint64_t* item, uint64_t ncand, hipStream_t s);
 hipError_t launch_accept_inc_src(const AcceptArrays& a, uint64_t ncand, uint64_t ninc, uint64_t* inc_src, hipStream_t s);
-hipError_t launch_accept_missing(const IndexTable& t, const uint64_t* item, uint64_t ninc, uint64_t* wgcount,
-                                 uint64_t* wgbase, uint64_t* ctl, uint64_t* out, uint64_t cap, hipStream_t s);
+hipError_t launch_accept_missing(const IndexTable& t, const uint64_t* item, uint64_t ninc, uint64_t* wg, uint64_t* ctl,
+                                 uint64_t* out, uint64_t cap, hipStream_t s);
 
-// The suspended-block store (mv_connect_blocks; layout and sweep: index.hip): one record per block
+// The suspended-block store (mv_connect_blocks; layout and sweep: pending.hip): one record per block
 // whose includes are not all MV_REF_STORED, in arrival order. The engine keeps two copies and
 // compacts from one into the other. References are held as slots of the table: a rebuild
 // re-resolves them (launch_pend_reresolve).
@@ -528,23 +544,23 @@ hipError_t launch_pend_own_slots(const uint64_t* item, uint64_t ncand, uint64_t*
 // order; item: the records of the includes' insert. ctl[IX_CTL_PB_NB], ctl[IX_CTL_PB_NI] = how many.
 hipError_t launch_pend_append(const AcceptArrays& a, uint64_t ncand, uint64_t ninc, const uint64_t* item,
                               const uint64_t* cand_slot, uint64_t* cand_dst, const PendStore& p, uint64_t nb0, uint64_t ni0,
-                              uint64_t* wg /* 4 x index_groups(ncand) */, uint64_t* ctl, hipStream_t s);
+                              uint64_t* wg, uint64_t* ctl, hipStream_t s);
 // One level of the sweep over the nb records: check (a wave per record), count, scan, list + raise.
 // lvl[b]: 0, or 1 + the level that connected b. Rows go to out (cap rows of 8 words) from row
 // ctl[IX_CTL_PB_ROWS] on; ctl[lv_word] = the rows of this level. row_of (may be null; per record):
 // the row a record connected as, whatever the cap -- the DAG store's record order.
 hipError_t launch_pend_level(const IndexTable& t, const PendStore& p, uint64_t nb, uint32_t* lvl, uint8_t* hit,
-                             uint64_t level, uint64_t* wg /* 2 x index_groups(nb) */, uint64_t* out, uint64_t cap,
+                             uint64_t level, uint64_t* wg, uint64_t* out, uint64_t cap,
                              uint64_t* ctl, int lv_word, uint32_t* row_of, hipStream_t s);
 // Stable compaction of p's records that are not STORED into q; those of the running call become
 // MV_ACC_SUSPENDED in state (n_state entries, may be null). ctl[IX_CTL_PB_NB], ctl[IX_CTL_PB_NI] = what q holds.
 hipError_t launch_pend_compact(const IndexTable& t, const PendStore& p, const PendStore& q, uint64_t nb, uint64_t* newbase,
-                               uint8_t* state, uint64_t n_state, uint64_t* wg /* 4 x index_groups(nb) */, uint64_t* ctl, hipStream_t s);
+                               uint8_t* state, uint64_t n_state, uint64_t* wg, uint64_t* ctl, hipStream_t s);
 // after launch_index_rebuild: n slot numbers of the old table become those of the same keys in t
 hipError_t launch_pend_reresolve(const uint64_t* old_slots, const IndexTable& t, uint64_t* slotidx, uint64_t n,
                                  uint64_t* ctl, hipStream_t s);
 
-// The DAG store (mv_dag_reserve, mv_decide_leaders; kernels and memory model: index.hip): one
+// The DAG store (mv_dag_reserve, mv_decide_leaders; kernels: dag_store.hip, decide.hip): one
 // record per block that mv_connect_blocks stored, in connected-row order, with its includes as
 // slots of the table. map: per slot of the table the record of its reference, DG_NONE without one.
 struct DagStore {
@@ -563,7 +579,7 @@ constexpr uint32_t DG_MAX_AUTH = 512;  // the bitmaps are 16 words (the walk's t
 constexpr int DG_BM_WORDS = DG_MAX_AUTH / 32;
 // The rows of a connect call (records of p with lvl != 0, row row_of[b]) join d behind its nb0
 // records and ni0 includes: the records, the scan of their include counts (ctl[IX_CTL_DG_NI] = the
-// includes), the include slots a wave per row. src: rows words of scratch; wg: 2 x index_groups(rows).
+// includes), the include slots a wave per row. src: rows words of scratch.
 hipError_t launch_dag_append(const IndexTable& t, const PendStore& p, uint64_t nb, const uint32_t* lvl,
                              const uint32_t* row_of, uint64_t rows, const DagStore& d, uint64_t nb0, uint64_t ni0,
                              uint64_t* src, uint64_t* wg, uint64_t* ctl, hipStream_t s);
@@ -572,9 +588,9 @@ hipError_t launch_dag_map(const DagStore& d, uint64_t nb, uint64_t* ctl, hipStre
 // Stable compaction of d's records of round >= floor into q (whose map is rebuilt);
 // ctl[IX_CTL_DG_NB], ctl[IX_CTL_DG_NI] = what q holds, ctl[IX_CTL_DG_NLO / _HI] its rounds.
 hipError_t launch_dag_prune(const DagStore& d, const DagStore& q, uint64_t nb, uint64_t floor, uint64_t* newbase,
-                            uint64_t* wg /* 4 x index_groups(nb) */, uint64_t* ctl, hipStream_t s);
+                            uint64_t* wg, uint64_t* ctl, hipStream_t s);
 
-// One seed call (mv_dev_dag_seed_rows, mv_wal_recover; kernels: index.hip): the rows of a replay
+// One seed call (mv_dev_dag_seed_rows, mv_wal_recover; kernels: dag_store.hip): the rows of a replay
 // (n x SD_ROW_WORDS words: 1 the offset of the block's bincode in img, 2 its length, 3..8 its
 // reference) with their block verdicts, and the per-row scratch. Offsets and lengths are the
 // caller's: every one is checked against `size` before a byte of img is read.
@@ -595,12 +611,12 @@ struct SeedRows {
 constexpr int IX_CTL_SD_NREC = IX_CTL_NVER, IX_CTL_SD_MISFIT = IX_CTL_NHEADS, IX_CTL_SD_ELIG = IX_CTL_NCAND,
               IX_CTL_SD_EINC = IX_CTL_NINC, IX_CTL_SD_NINC = IX_CTL_NWANTED;
 // k_sd_elig and its scans: elig, kc; ctl[IX_CTL_SD_ELIG / _EINC] = the eligible rows and their includes,
-// ctl[IX_CTL_SD_MISFIT] += the misfits (wg: 4 x index_groups(n))
+// ctl[IX_CTL_SD_MISFIT] += the misfits
 hipError_t launch_seed_eligible(const SeedRows& r, uint64_t* wg, uint64_t* ctl, hipStream_t s);
 // after the own references' insert (item: its records): k_sd_claim, k_sd_count, the scans, k_sd_list.
 // The record rows join d behind its nb0 records and ni0 includes; ctl[IX_CTL_SD_NREC / _NINC] = how many.
 hipError_t launch_seed_records(const IndexTable& t, const uint64_t* item, const SeedRows& r, const DagStore& d, uint64_t nb0,
-                               uint64_t ni0, uint64_t* wg /* 4 x index_groups(n) */, uint64_t* ctl, hipStream_t s);
+                               uint64_t ni0, uint64_t* wg, uint64_t* ctl, hipStream_t s);
 // inc_src[j] = where include item j of the call's nrec records lies in img (IX_NO_SRC for none)
 hipError_t launch_seed_inc_src(const SeedRows& r, const DagStore& d, uint64_t nb0, uint64_t ni0, uint64_t nrec, uint64_t ninc,
                                uint64_t* inc_src, uint64_t* ctl, hipStream_t s);
@@ -634,14 +650,14 @@ struct DecideState {  // zeroed by the caller except vpos / vlist / dlist / sup
 };
 // k_dg_pick: vpos, vlist, dlist, the candidates; ctl[IX_CTL_DG_NVOTE], ctl[IX_CTL_DG_NDEC]
 hipError_t launch_decide_pick(const DagStore& d, uint64_t nb, const DecideIn& in, const DecideState& st,
-                              uint64_t* wg /* 4 x index_groups(nb) */, uint64_t* ctl, hipStream_t s);
+                              uint64_t* wg, uint64_t* ctl, hipStream_t s);
 // k_dg_vote, k_dg_cert, k_dg_decide: out (n x 8) and stakes_out (n x 3, may be null) in the caller's row order
 hipError_t launch_decide_rule(const IndexTable& t, const DagStore& d, uint64_t nb, const DecideIn& in,
                               const DecideState& st, uint64_t nvote, uint64_t ndec, const uint64_t* stakes,
                               uint32_t n_auth, uint64_t quorum_thr, uint64_t* out, uint64_t* stakes_out, uint64_t* ctl,
                               hipStream_t s);
 
-// One commit call (mv_commit_leaders; kernels: index.hip) on top of a decide call's DecideIn /
+// One commit call (mv_commit_leaders; kernels: decide.hip) on top of a decide call's DecideIn /
 // DecideState and its out rows, which must be in non-decreasing round order (l_row[k] = k). All
 // arrays are per row unless said otherwise.
 struct CommitState {
@@ -665,7 +681,7 @@ hipError_t launch_commit_init(const IndexTable& t, const DecideIn& in, const Dec
 // one pass's chain step: act, anchor, the jobs; ctl[IX_CTL_CM_NJOBS / _QHI / _NQLO / _MOVED] (zeroed by the caller,
 // as job_id (all ones), job_low (all ones) and job_miss (0) are)
 hipError_t launch_commit_chain(const DecideIn& in, const CommitState& cs, const uint64_t* out, uint64_t* ctl, hipStream_t s);
-// span = the records of rounds lo..hi; ctl[IX_CTL_CM_NSPAN] = how many (wg: 2 x index_groups(nb))
+// span = the records of rounds lo..hi; ctl[IX_CTL_CM_NSPAN] = how many
 hipError_t launch_commit_span(const DagStore& d, uint64_t nb, uint64_t lo, uint64_t hi, uint32_t* span, uint64_t* wg,
                               uint64_t* ctl, hipStream_t s);
 // the anchors' records into the (zeroed) marks, then one launch over the span per level of `levels` (descending)

@@ -247,6 +247,69 @@ def test_include_counts_at_the_lane_edges(engine, committee70, k):
         engine.index_clear()
 
 
+# ---------------------------------------------------------------- 7b. levels wider than a workgroup
+@pytest.fixture(scope="module")
+def wide(engine):
+    """Three rounds of 260 authorities (more than a workgroup of 256 records per round), each block
+    with its own block of the round before and one other's; authority 0 holds the stake, as above."""
+    n = 260
+    seeds = [MB.authority_seed(a) for a in range(n)]
+    pks, _ = MB.committee(engine, n, distinct=True)
+    stakes = np.ones(n, dtype=np.uint64)
+    stakes[0] = 4 * n
+    bins = MB.build_rounds(engine, 3, n, seeds, n_inc=2, n_vr=0, with_tx=False)
+    return (bins, (pks, stakes, 0), MB.genesis_refs(n), RM.oracle_verdicts(pks, stakes, 0)), n
+
+
+@pytest.fixture
+def wide_eng(engine, wide):
+    engine.set_committee(*wide[0][1])
+    engine.index_clear()
+    yield engine
+    engine.index_clear()
+
+
+def wide_model(e, wide):
+    corpus, n = wide
+    assert e.index_insert_stored(corpus[2]).tolist() == [0] * n
+    return CM.ThreeState(corpus[3], corpus[2], CM.STORED)
+
+
+def test_three_levels_of_more_than_a_workgroup(wide_eng, wide):
+    """One shuffled call: level 0 lists 260 rows, and the scans of levels 1 and 2 place theirs, from
+    three workgroups of records each, behind the rows so far. Rows, levels and order are the model's."""
+    corpus, n = wide
+    three = wide_model(wide_eng, wide)
+    order = list(range(3 * n))
+    random.Random(7).shuffle(order)
+    got, _ = connect(wide_eng, three, corpus, [corpus[0][i] for i in order], None, "wide")
+    assert got.n_connected == 3 * n and got.connected[:, 7].tolist() == [0] * n + [1] * n + [2] * n
+    for lv in range(3):  # within a level: arrival order
+        at = got.connected[lv * n:(lv + 1) * n, 6].tolist()
+        assert at == sorted(at) and all(order[int(i)] // n == lv for i in at)
+    assert wide_eng.pending_stats().levels == 3
+
+
+def test_one_parent_releases_more_than_a_workgroup(wide_eng, wide):
+    """Rounds 2 and 3 wait, shuffled together, for authority 0's blocks of rounds 1 and 2. Its block
+    of round 1 releases 259 blocks of round 2 in one level; the 260 of round 3 stay, interleaved
+    with them, and the compaction keeps each with its includes: its block of round 2 releases them."""
+    corpus, n = wide
+    bins = corpus[0]
+    three = wide_model(wide_eng, wide)
+    late = [i for i in range(n, 3 * n) if i != n]
+    random.Random(8).shuffle(late)
+    got, _ = connect(wide_eng, three, corpus, bins[1:n] + [bins[i] for i in late], None, "waiting")
+    assert got.n_connected == n - 1 and wide_eng.pending_stats().suspended == 2 * n - 1
+    got, _ = connect(wide_eng, three, corpus, [bins[0]], None, "round 1")
+    assert got.connected[:, 7].tolist() == [0] + [1] * (n - 1) and wide_eng.pending_stats().suspended == n
+    assert all(int(r[1]) == 2 and int(r[6]) == EARLIER for r in got.connected[1:])
+    got, _ = connect(wide_eng, three, corpus, [bins[n]], None, "round 2")
+    assert got.connected[:, 7].tolist() == [0] + [1] * n and wide_eng.pending_stats().suspended == 0
+    want = [IM.own_ref(bins[i]) for i in late if i >= 2 * n]  # in arrival order
+    assert [IM.words_ref(r[:6]) for r in got.connected[1:]] == want
+
+
 # ---------------------------------------------------------------- 8. the device call
 def dev_connect(e, blocks, groups, cap, cap_rows, pad=16):
     """mv_dev_connect_blocks on a device buffer that ends `pad` bytes after the last block."""

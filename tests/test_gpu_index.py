@@ -203,6 +203,27 @@ def test_growth_keeps_every_entry(engine):
         e.close()
 
 
+def test_wanted_list_of_a_large_table(engine):
+    """A table of 2^19 slots is 2048 workgroups of the WANTED count: each lane of the scan's one
+    workgroup sums two of them (tables up to 2^18 slots give a lane one at most). 257 and 513
+    WANTED entries lie scattered over all of them, with HAVE entries in between that are not listed."""
+    e = M.Engine(devices=(0,))
+    try:
+        e.index_reserve(1 << 18)
+        assert e.index_stats().capacity == 1 << 18
+        for n in (257, 513):
+            rng = random.Random(n)
+            two = IM.TwoState(None)
+            for refs, st in ((rand_refs(rng, n), M.REF_WANTED), (rand_refs(rng, 300), M.REF_HAVE)):
+                assert e.index_insert(refs, st).tolist() == two.insert(refs, st)
+            assert two.counts()[1] == n
+            check_index(e, two, n)  # the listed set is the model's, and its count is n
+            e.index_clear()
+        assert e.index_stats().capacity == 1 << 18 and e.index_stats().rebuilds == 0
+    finally:
+        e.close()
+
+
 # ---------------------------------------------------------------- attacker-shaped keys
 def test_keys_that_differ_in_one_byte(eng64):
     """48 x 255 references that differ from one base in a single byte, every position and value: a

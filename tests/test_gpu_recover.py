@@ -299,6 +299,50 @@ def test_many_rows(rec_engine, long7):
     check(e.commit_leaders(leaders), model.rule(dag.stakes), leaders, "many")
 
 
+@pytest.fixture(scope="module")
+def longer7(engine):
+    """80 rounds of 7: 560 records, three workgroups of 256 with the last one partial."""
+    d = Dag(engine, 7, [1] * 7, distinct=True)
+    refs = {(a, 0, 0): d.genesis[a] for a in range(7)}
+    for rnd, layer in enumerate(valid_random_dag(6, 7, 80), 1):
+        made, seen = d.layer([(a, [refs[i] for i in incs]) for a, incs in layer]), {}
+        for (a, _), ref in zip(layer, made):
+            refs[(a, rnd, seen.get(a, 0))] = ref
+            seen[a] = seen.get(a, 0) + 1
+    return d
+
+
+def test_records_across_workgroups(rec_engine, longer7):
+    """For the leaders around the rounds of records 256 and 512 the voting and decision records, and
+    the rounds a walk reads, lie on both sides of a workgroup's edge, in the seeded rows, in the pick
+    lists and in the span. Then a prune whose floor cuts through the
+    store: what it keeps starts in the second workgroup and fills more than one."""
+    dag, e = longer7, rec_engine
+    assert len(dag.bins) >= 513
+    blank(e, 64, dag)
+    blocks = genesis_bins(dag.n) + dag.bins
+    model, seeded, want = recover(e, dag, blocks)
+    assert seeded.records == len(dag.bins)
+    all_leaders = rows_of(S.PIPELINED_TWO, dag)
+
+    def around(store, k):  # the leaders whose voting or decision round holds record k of the store
+        r = store.records[k][0][1]
+        return [x for x in all_leaders if r - 3 <= x[1] <= r + 1]
+
+    for k in (256, 512):
+        leaders = around(model, k)
+        assert len(leaders) == 10
+        check(e.commit_leaders(leaders), model.rule(dag.stakes), leaders, f"around record {k}")
+    floor = 40
+    pruned = RC.Store()
+    pruned.seed(wal_of(blocks, 12)[0], want.rows, want.blk_status, floor)
+    e.dag_prune(floor)
+    assert stats_of(e) == pruned.stats() and 256 < pruned.stats()[0] < len(dag.bins) - 256
+    leaders = around(pruned, 256)
+    assert len(leaders) == 10
+    check(e.commit_leaders(leaders), pruned.rule(dag.stakes), leaders, "pruned")
+
+
 # ---------------------------------------------------------------- 6. a truncated history
 def test_truncated_history(rec_engine, random7, tag):
     dag, e = random7, rec_engine
