@@ -41,6 +41,7 @@
 
 #include "fe25519.h"
 #include "ge25519.h"
+#include "blake2b_quad.h"
 #include "hash_dev.h"
 #include "kernels.h"
 #include "scalar25519.h"
@@ -233,8 +234,8 @@ __global__ void __launch_bounds__(256, MV_PREP_OCC)
     m[5] = gid;
 #pragma unroll
     for (int i = 6; i < 16; i++) m[i] = 0;
-    b2_init256(h);
-    b2_compress(h, m, 48, true);
+    b2q::lane_init256(h);
+    b2q::lane_compress(h, m, 48, true);
     z[0] = (uint32_t)h[0];
     z[1] = (uint32_t)(h[0] >> 32);
     z[2] = (uint32_t)h[1];

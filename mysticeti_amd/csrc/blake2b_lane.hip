@@ -30,49 +30,7 @@
 namespace mv {
 namespace b2l {
 
-using b2q::add64;
-using b2q::IV;
 using b2q::Plan;
-using b2q::ror16;
-using b2q::ror24;
-using b2q::ror32;
-using b2q::ror63;
-using b2q::SIGMA;
-
-#define MV_LG(a, b, c, d, x, y) \
-  a = add64(add64(a, b), x);    \
-  d = ror32(d ^ a);             \
-  c = add64(c, d);              \
-  b = ror24(b ^ c);             \
-  a = add64(add64(a, b), y);    \
-  d = ror16(d ^ a);             \
-  c = add64(c, d);              \
-  b = ror63(b ^ c);
-
-MV_DEV void compress(uint64_t (&h)[8], const uint64_t (&m)[16], uint64_t t, bool fin) {
-  uint64_t v[16];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    v[i] = h[i];
-    v[8 + i] = IV[i];
-  }
-  v[12] ^= t;  // t < 2^64: v[13] unchanged
-  v[14] = fin ? ~v[14] : v[14];
-#pragma unroll
-  for (int r = 0; r < 12; r++) {
-    MV_LG(v[0], v[4], v[8], v[12], m[SIGMA[r][0]], m[SIGMA[r][1]])
-    MV_LG(v[1], v[5], v[9], v[13], m[SIGMA[r][2]], m[SIGMA[r][3]])
-    MV_LG(v[2], v[6], v[10], v[14], m[SIGMA[r][4]], m[SIGMA[r][5]])
-    MV_LG(v[3], v[7], v[11], v[15], m[SIGMA[r][6]], m[SIGMA[r][7]])
-    MV_LG(v[0], v[5], v[10], v[15], m[SIGMA[r][8]], m[SIGMA[r][9]])
-    MV_LG(v[1], v[6], v[11], v[12], m[SIGMA[r][10]], m[SIGMA[r][11]])
-    MV_LG(v[2], v[7], v[8], v[13], m[SIGMA[r][12]], m[SIGMA[r][13]])
-    MV_LG(v[3], v[4], v[9], v[14], m[SIGMA[r][14]], m[SIGMA[r][15]])
-  }
-#pragma unroll
-  for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
-}
-#undef MV_LG
 
 // Block b of the string at p, zero past lim; a word is read only when it starts below lim (the
 // strings are 8-aligned and readable up to round-up(lim, 8), as for the quad form).
@@ -121,9 +79,7 @@ __global__ void __launch_bounds__(64) k_b2_lane(const uint8_t* __restrict__ buf,
   const uint8_t* p = buf + (live ? off[i] : 0);
   const uint32_t nmax = b2q::wave_max(pl.nsteps);
   uint64_t h[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) h[k] = IV[k];
-  h[0] ^= 0x01010020ull;  // depth 1, fanout 1, nn = 32
+  b2q::lane_init256(h);
   for (uint32_t s = 0; s < nmax; s++) {
     uint64_t b, lim, t;
     bool fin, mfin;
@@ -133,7 +89,7 @@ __global__ void __launch_bounds__(64) k_b2_lane(const uint8_t* __restrict__ buf,
     uint64_t hs[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) hs[k] = h[k];
-    compress(h, m, t, fin);
+    b2q::lane_compress(h, m, t, fin);
     if (DUAL && mfin && s < pl.nsteps) {
       uint64_t* o = reinterpret_cast<uint64_t*>(out0 + 32 * (size_t)i);
 #pragma unroll

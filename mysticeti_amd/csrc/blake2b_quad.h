@@ -1,5 +1,7 @@
-// BLAKE2b-256 with FOUR lanes per string: the device code of blake2b_quad.hip (its header
-// comment describes the design), shared with comb.hip's latency-path kernel.
+// BLAKE2b-256 device code. The one statement of IV, SIGMA, the parameter word and the rotations;
+// on them the ONE-lane-per-string compression (lane_*: blake2b_lane.hip, block_walk.hip, seal.hip,
+// batch.hip) and the FOUR-lanes-per-string form of blake2b_quad.hip (its header comment describes
+// the design), shared with comb.hip's latency-path kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,6 +84,63 @@ MV_DEV uint64_t ror63(uint64_t x) {
   const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
   return pack(__builtin_amdgcn_alignbit(lo, hi, 31), __builtin_amdgcn_alignbit(hi, lo, 31));
 }
+// ---------------------------------------------------------------- one lane per string
+// The whole compression in one lane: v[16], h[8] and the block's 16 words m in registers, SIGMA
+// resolved at compile time. Every one-lane user (blake2b_lane.hip, block_walk.hip, the seal
+// stream, k_bv_prep's coefficients) hashes through these.
+constexpr uint64_t PARAM256 = 0x01010020ull;  // depth 1, fanout 1, no key, nn = 32: xored into h[0]
+
+MV_DEV void lane_init256(uint64_t (&h)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) h[i] = IV[i];
+  h[0] ^= PARAM256;
+}
+// G on four state words and two message words (RFC 7693 §3.1)
+MV_DEV void lane_g(uint64_t& a, uint64_t& b, uint64_t& c, uint64_t& d, uint64_t x, uint64_t y) {
+  a = add64(add64(a, b), x);
+  d = ror32(d ^ a);
+  c = add64(c, d);
+  b = ror24(b ^ c);
+  a = add64(add64(a, b), y);
+  d = ror16(d ^ a);
+  c = add64(c, d);
+  b = ror63(b ^ c);
+}
+// v = the 12 rounds on (h || IV with the counter t < 2^64 and the final flag) and m
+MV_DEV void lane_rounds(uint64_t (&v)[16], const uint64_t (&h)[8], const uint64_t (&m)[16], uint64_t t, bool fin) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    v[i] = h[i];
+    v[8 + i] = IV[i];
+  }
+  v[12] ^= t;
+  v[14] = fin ? ~v[14] : v[14];
+#pragma unroll
+  for (int r = 0; r < 12; r++) {
+    lane_g(v[0], v[4], v[8], v[12], m[SIGMA[r][0]], m[SIGMA[r][1]]);
+    lane_g(v[1], v[5], v[9], v[13], m[SIGMA[r][2]], m[SIGMA[r][3]]);
+    lane_g(v[2], v[6], v[10], v[14], m[SIGMA[r][4]], m[SIGMA[r][5]]);
+    lane_g(v[3], v[7], v[11], v[15], m[SIGMA[r][6]], m[SIGMA[r][7]]);
+    lane_g(v[0], v[5], v[10], v[15], m[SIGMA[r][8]], m[SIGMA[r][9]]);
+    lane_g(v[1], v[6], v[11], v[12], m[SIGMA[r][10]], m[SIGMA[r][11]]);
+    lane_g(v[2], v[7], v[8], v[13], m[SIGMA[r][12]], m[SIGMA[r][13]]);
+    lane_g(v[3], v[4], v[9], v[14], m[SIGMA[r][14]], m[SIGMA[r][15]]);
+  }
+}
+// the chaining state after the rounds: all of it into h, or its word k alone (h stays)
+MV_DEV void lane_fold(uint64_t (&h)[8], const uint64_t (&v)[16]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
+}
+MV_DEV uint64_t lane_word(const uint64_t (&h)[8], const uint64_t (&v)[16], int k) { return h[k] ^ v[k] ^ v[8 + k]; }
+// m[16] little-endian message words; t = bytes hashed so far including this block
+MV_DEV void lane_compress(uint64_t (&h)[8], const uint64_t (&m)[16], uint64_t t, bool fin) {
+  uint64_t v[16];
+  lane_rounds(v, h, m, t, fin);
+  lane_fold(h, v);
+}
+
+// ---------------------------------------------------------------- four lanes per string
 // lane q of each quad takes x from lane (q + K) & 3
 template <int K>
 MV_DEV uint64_t qrot(uint64_t x) {
@@ -285,7 +344,7 @@ MV_DEV void quad_hash_range(uint32_t first, uint32_t count, const uint8_t* __res
   uint64_t h0[NS], h1[NS];
 #pragma unroll
   for (int k = 0; k < NS; k++) {
-    h0[k] = iv0 ^ (q == 0 ? 0x01010020ull : 0ull);  // depth 1, fanout 1, nn = 32
+    h0[k] = iv0 ^ (q == 0 ? PARAM256 : 0ull);
     h1[k] = iv1;
   }
   uint64_t w[NS][4];

@@ -19,7 +19,7 @@
 //
 // Any failed read or check (a length past the block, a digest length other than 32, an
 // unknown tag, vote or option, an epoch marker > 1, a signature length other than 64) makes
-// the block a parse error, as ingest_lane's BcReader does: which check fails first never
+// the block a parse error, as the shared walk's BcReader does (bincode_walk.h): which check fails first never
 // matters, because every failure gives the same verdict (MV_BLOCK_PARSE_ERROR, digests zeroed
 // by k_block_verdict). tests/test_gpu_ingest.py runs every ingest case through this kernel
 // (the batch_walk form) against the host codec and the oracle.
@@ -34,20 +34,11 @@
 namespace mv {
 namespace bw {
 
-using b2q::add64;
-using b2q::IV;
-using b2q::ror16;
-using b2q::ror24;
-using b2q::ror32;
-using b2q::ror63;
-using b2q::SIGMA;
-
 #ifndef MV_WALK_ROW
 #define MV_WALK_ROW 200  // (A/B builds may pad it to trade occupancy for L2 footprint)
 #endif
 constexpr uint32_t ROW = MV_WALK_ROW;  // bytes per lane: one message block + the longest piece (72 B)
 static_assert(ROW >= 200 && ROW % 8 == 0, "a row holds a block and the longest piece");
-constexpr uint64_t VR_MAX = 1024 * 1024;  // VoteRange::verify MAX_LEN (types.rs:448)
 
 MV_DEV uint64_t ld64(const uint8_t* p) {
   uint64_t v;
@@ -60,11 +51,6 @@ MV_DEV void st_be(uint8_t* q, uint64_t v) { st64(q, __builtin_bswap64(v)); }
 enum : uint32_t { HDR, INC, NST, STMT, META, SIG, DONE };
 constexpr uint32_t SUB_NONE = 0, SUB_SHARE = 1, SUB_REJ2 = 2;
 
-struct CommitteeArgs {
-  const uint64_t* stakes;
-  uint32_t n_auth;
-  uint64_t epoch, quorum_thr;
-};
 struct BlockOut {
   uint8_t* sig;
   uint32_t* key_idx;
@@ -143,7 +129,7 @@ MV_DEV void st_dig(uint8_t* q, const Window& wn) {
 // checks of the element it belongs to; clears w.ok on the first failure. Returns the piece's
 // length.
 template <int NW>
-MV_DEV uint32_t piece(Walk<NW>& w, uint8_t* q, const CommitteeArgs& ca, const Window& wn) {
+MV_DEV uint32_t piece(Walk<NW>& w, uint8_t* q, const CommitteeView& ca, const Window& wn) {
   if (w.phase == HDR) {  // own reference (author, round, digest) and the include count
     if (!w.fits(0, 64)) {
       w.ok = false;
@@ -167,10 +153,8 @@ MV_DEV uint32_t piece(Walk<NW>& w, uint8_t* q, const CommitteeArgs& ca, const Wi
     st_be(q, a);
     st_be(q + 8, r);
     st_dig<0>(q + 16, wn);
-    if (w.inc_code == 0)
-      w.inc_code = a >= ca.n_auth ? (uint32_t)MV_BLOCK_INCLUDE_UNKNOWN_AUTHORITY
-                                  : (r >= w.me_r ? (uint32_t)MV_BLOCK_INCLUDE_ROUND : 0u);
-    if (w.me_r > 0 && r == w.me_r - 1 && a < ca.n_auth) {
+    if (w.inc_code == 0) w.inc_code = include_code(a, r, w.me_r, ca.n_auth);
+    if (clock_include(a, r, w.me_r, ca.n_auth)) {
       const uint32_t wdx = (uint32_t)a >> 5, bit = 1u << (a & 31);
       uint32_t s = 0;
 #pragma unroll
@@ -268,7 +252,7 @@ MV_DEV uint32_t piece(Walk<NW>& w, uint8_t* q, const CommitteeArgs& ca, const Wi
         st_dig<4>(q + 17, wn);
         st_be(q + 49, s0);
         st_be(q + 57, s1);
-        if (w.vr_code == 0) w.vr_code = s1 < s0 ? 1u : (s1 - s0 >= VR_MAX ? 2u : (s1 >= VR_MAX ? 3u : 0u));
+        if (w.vr_code == 0) w.vr_code = vr_code(s0, s1);
         w.src += 76;
         n = 65;
       } else {
@@ -298,21 +282,10 @@ MV_DEV uint32_t piece(Walk<NW>& w, uint8_t* q, const CommitteeArgs& ca, const Wi
   return 25;
 }
 
-// MV_LG: BLAKE2b's G on four state words and two message words (RFC 7693 §3.1)
-#define MV_LG(a, bb, c, d, x, y) \
-  a = add64(add64(a, bb), x);    \
-  d = ror32(d ^ a);              \
-  c = add64(c, d);               \
-  bb = ror24(bb ^ c);            \
-  a = add64(add64(a, bb), y);    \
-  d = ror16(d ^ a);              \
-  c = add64(c, d);               \
-  bb = ror63(bb ^ c);
-
 // Blocks [0, n) of buf at off[i] (len[i] bytes), 64 per 64-lane workgroup.
 template <int NW>
 __global__ void __launch_bounds__(64) k_block_walk(const uint8_t* __restrict__ buf, const uint64_t* __restrict__ off,
-                                                   const uint64_t* __restrict__ len, uint32_t n, CommitteeArgs ca,
+                                                   const uint64_t* __restrict__ len, uint32_t n, CommitteeView ca,
                                                    BlockOut out) {
   __shared__ uint64_t rows[64 * ROW / 8];
   const uint32_t lane = threadIdx.x;
@@ -338,9 +311,7 @@ __global__ void __launch_bounds__(64) k_block_walk(const uint8_t* __restrict__ b
   uint32_t pos = 0, plen = 0;
   uint64_t blocks = 0;  // message blocks of P || sig compressed so far
   uint64_t h[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) h[k] = IV[k];
-  h[0] ^= 0x01010020ull;  // depth 1, fanout 1, nn = 32
+  b2q::lane_init256(h);
   while (__ballot(live)) {
     // fill the row up to a whole block, P's end (its final block goes first), or the end
     while (live && w.ok && pos < 128 && w.phase != DONE) {
@@ -374,37 +345,19 @@ __global__ void __launch_bounds__(64) k_block_walk(const uint8_t* __restrict__ b
       m[j] = v;
     }
     uint64_t v[16];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      v[k] = h[k];
-      v[8 + k] = IV[k];
-    }
-    v[12] ^= t;
-    v[14] = mfin || fin ? ~v[14] : v[14];
-#pragma unroll
-    for (int r = 0; r < 12; r++) {
-      MV_LG(v[0], v[4], v[8], v[12], m[SIGMA[r][0]], m[SIGMA[r][1]])
-      MV_LG(v[1], v[5], v[9], v[13], m[SIGMA[r][2]], m[SIGMA[r][3]])
-      MV_LG(v[2], v[6], v[10], v[14], m[SIGMA[r][4]], m[SIGMA[r][5]])
-      MV_LG(v[3], v[7], v[11], v[15], m[SIGMA[r][6]], m[SIGMA[r][7]])
-      MV_LG(v[0], v[5], v[10], v[15], m[SIGMA[r][8]], m[SIGMA[r][9]])
-      MV_LG(v[1], v[6], v[11], v[12], m[SIGMA[r][10]], m[SIGMA[r][11]])
-      MV_LG(v[2], v[7], v[8], v[13], m[SIGMA[r][12]], m[SIGMA[r][13]])
-      MV_LG(v[3], v[4], v[9], v[14], m[SIGMA[r][14]], m[SIGMA[r][15]])
-    }
+    b2q::lane_rounds(v, h, m, t, mfin || fin);
     if (mfin) {  // B2(P) = msg
       uint64_t* o = reinterpret_cast<uint64_t*>(out.md + 32 * (size_t)i);
 #pragma unroll
-      for (int k = 0; k < 4; k++) o[k] = h[k] ^ v[k] ^ v[8 + k];
+      for (int k = 0; k < 4; k++) o[k] = b2q::lane_word(h, v, k);
       pdone = true;
     } else if (fin) {  // B2(P || sig) = the block digest
       uint64_t* o = reinterpret_cast<uint64_t*>(out.bd + 32 * (size_t)i);
 #pragma unroll
-      for (int k = 0; k < 4; k++) o[k] = h[k] ^ v[k] ^ v[8 + k];
+      for (int k = 0; k < 4; k++) o[k] = b2q::lane_word(h, v, k);
       live = false;
     } else if (live) {
-#pragma unroll
-      for (int k = 0; k < 8; k++) h[k] ^= v[k] ^ v[8 + k];
+      b2q::lane_fold(h, v);
       blocks++;
       // the bytes emitted past the block move to the row's start
 #pragma unroll
@@ -413,36 +366,22 @@ __global__ void __launch_bounds__(64) k_block_walk(const uint8_t* __restrict__ b
     }
   }
   if (i >= n) return;
-  // per-block outputs (ingest_lane's): facts, claimed digest, signature (s = 2^256 - 1 unless
-  // the signature decides the verdict), key index
+  // per-block outputs: facts, signature, claimed digest, key index (block_verdict.h)
   const bool parsed = w.ok && w.phase == DONE;
   uint32_t f = 0;
   if (parsed)
-    f = BF_PARSED | (ld64(w.blk + w.src + 17) == ca.epoch ? BF_EPOCH_OK : 0u) |
-        (w.me_a < ca.n_auth ? BF_AUTHOR_OK : 0u) | (w.me_r == 0 ? BF_GENESIS : 0u) | (w.vr_code << BF_VR_SHIFT) |
-        (w.stake > ca.quorum_thr ? BF_QUORUM : 0u) | (w.inc_code << BF_INC_SHIFT);
-  const bool sig_decides = parsed && (f & BF_EPOCH_OK) && (f & BF_AUTHOR_OK) && !(f & BF_GENESIS);
-  uint64_t sw[8];
+    f = block_facts(ld64(w.blk + w.src + 17) == ca.epoch, w.me_a < ca.n_auth, w.me_r == 0, w.vr_code,
+                    w.stake > ca.quorum_thr, w.inc_code);
+  uint32_t sw[16];
 #pragma unroll
   for (int q = 0; q < 8; q++) {
-    sw[q] = parsed ? ld64(w.blk + w.src + 33 + 8 * q) : 0ull;
-    if (q >= 4 && !sig_decides) sw[q] = ~0ull;
+    const uint64_t x = parsed ? ld64(w.blk + w.src + 33 + 8 * q) : 0ull;
+    sw[2 * q] = (uint32_t)x;
+    sw[2 * q + 1] = (uint32_t)(x >> 32);
   }
-  uint4* so4 = reinterpret_cast<uint4*>(out.sig + 64 * (size_t)i);
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    so4[q] = make_uint4((uint32_t)sw[2 * q], (uint32_t)(sw[2 * q] >> 32), (uint32_t)sw[2 * q + 1],
-                        (uint32_t)(sw[2 * q + 1] >> 32));
-  if (parsed) {
-    uint4* cd = reinterpret_cast<uint4*>(out.claimed + 32 * (size_t)i);
-    const uint64_t d0 = ld64(w.blk + 24), d1 = ld64(w.blk + 32), d2 = ld64(w.blk + 40), d3 = ld64(w.blk + 48);
-    cd[0] = make_uint4((uint32_t)d0, (uint32_t)(d0 >> 32), (uint32_t)d1, (uint32_t)(d1 >> 32));
-    cd[1] = make_uint4((uint32_t)d2, (uint32_t)(d2 >> 32), (uint32_t)d3, (uint32_t)(d3 >> 32));
-  }
-  out.key_idx[i] = parsed && w.me_a < ca.n_auth ? w.me_a : 0u;
-  out.facts[i] = f;
+  store_block_outputs(i, f, w.me_a, sw, [&](int q) { return ld64(w.blk + 24 + 8 * q); }, out.sig, out.claimed,
+                      out.key_idx, out.facts);
 }
-#undef MV_LG
 
 }  // namespace bw
 }  // namespace mv
@@ -455,7 +394,7 @@ hipError_t launch_block_walk(const uint8_t* buf, const uint64_t* off, const uint
                              uint8_t* bd, hipStream_t s) {
   if (n == 0) return hipSuccess;
   if (n_auth > 512) return hipErrorInvalidValue;
-  const mv::bw::CommitteeArgs ca{stakes, n_auth, epoch, quorum_thr};
+  const mv::CommitteeView ca{stakes, n_auth, epoch, quorum_thr};
   const mv::bw::BlockOut out{sig, key_idx, facts, claimed, md, bd};
   if (n_auth <= 128)  // config 4's committee: a 4-word authority bitmap in VGPRs
     hipLaunchKernelGGL(mv::bw::k_block_walk<4>, dim3((n + 63) / 64), dim3(64), 0, s, buf, off, len, n, ca, out);

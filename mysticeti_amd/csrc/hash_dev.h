@@ -1,10 +1,8 @@
-// Per-lane SHA-512 (FIPS 180-4) and BLAKE2b (RFC 7693) compressions for gfx950.
+// Per-lane SHA-512 (FIPS 180-4) compression for gfx950 (BLAKE2b: blake2b_quad.h).
 //
 // SHA-512 is the ed25519 challenge hash k = H(R || A || M) (ed25519-consensus
-// 2.1.0 over sha2 0.9.9); BLAKE2b-256 is mysticeti's BlockHasher
-// (mysticeti-core/src/crypto.rs:34, Blake2b<U32>). 64-bit words are held as
-// VGPR pairs; rotations lower to v_alignbit_b32 pairs, 3-input logic to
-// v_bitop3_b32 (gfx950).
+// 2.1.0 over sha2 0.9.9). 64-bit words are held as VGPR pairs; rotations lower to
+// v_alignbit_b32 pairs, 3-input logic to v_bitop3_b32 (gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -193,65 +191,6 @@ MV_DEV void sha512_short(uint32_t out[16], const uint32_t* in, int nbytes) {
     out[2 * i] = (uint32_t)le;
     out[2 * i + 1] = (uint32_t)(le >> 32);
   }
-}
-
-// ---------------- BLAKE2b ----------------
-__constant__ const uint64_t B2_IV[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL,
-                                        0xa54ff53a5f1d36f1ULL, 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL,
-                                        0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
-
-MV_DEV void b2_init256(uint64_t h[8]) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) h[i] = B2_IV[i];
-  h[0] ^= 0x01010000ULL ^ 32ULL;  // depth 1, fanout 1, no key, 32-byte digest
-}
-
-#define MV_B2G(a, b, c, d, x, y)   \
-  do {                             \
-    v[a] = v[a] + v[b] + (x);      \
-    v[d] = rotr64(v[d] ^ v[a], 32); \
-    v[c] = v[c] + v[d];            \
-    v[b] = rotr64(v[b] ^ v[c], 24); \
-    v[a] = v[a] + v[b] + (y);      \
-    v[d] = rotr64(v[d] ^ v[a], 16); \
-    v[c] = v[c] + v[d];            \
-    v[b] = rotr64(v[b] ^ v[c], 63); \
-  } while (0)
-
-#define MV_B2ROUND(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15) \
-  MV_B2G(0, 4, 8, 12, m[s0], m[s1]);                                                     \
-  MV_B2G(1, 5, 9, 13, m[s2], m[s3]);                                                     \
-  MV_B2G(2, 6, 10, 14, m[s4], m[s5]);                                                    \
-  MV_B2G(3, 7, 11, 15, m[s6], m[s7]);                                                    \
-  MV_B2G(0, 5, 10, 15, m[s8], m[s9]);                                                    \
-  MV_B2G(1, 6, 11, 12, m[s10], m[s11]);                                                  \
-  MV_B2G(2, 7, 8, 13, m[s12], m[s13]);                                                   \
-  MV_B2G(3, 4, 9, 14, m[s14], m[s15]);
-
-// m[16] little-endian message words; t = bytes hashed so far incl. this block
-MV_DEV void b2_compress(uint64_t h[8], const uint64_t m[16], uint64_t t, bool last) {
-  uint64_t v[16];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    v[i] = h[i];
-    v[i + 8] = B2_IV[i];
-  }
-  v[12] ^= t;
-  v[14] = last ? ~v[14] : v[14];
-  MV_B2ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-  MV_B2ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
-  MV_B2ROUND(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
-  MV_B2ROUND(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
-  MV_B2ROUND(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
-  MV_B2ROUND(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
-  MV_B2ROUND(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
-  MV_B2ROUND(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
-  MV_B2ROUND(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
-  MV_B2ROUND(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
-  MV_B2ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-  MV_B2ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
-#pragma unroll
-  for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
 }
 
 }  // namespace mv

@@ -1,100 +1,22 @@
 // Device code of the block ingest, shared by ingest.hip's kernels and
 // the online committee verify (comb.hip's k_verify_comb16, which ingests its own blocks). The
-// rules and references are ingest.hip's header comment.
+// walk is bincode_walk.h's, the rules block_verdict.h's; the references are ingest.hip's header
+// comment.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/mysti_verify.h"
+#include "bincode_walk.h"
 #include "block_verdict.h"
-#include "hash_dev.h"
 
 namespace mv {
 
-constexpr uint64_t VR_MAX_LEN = 1024 * 1024;  // VoteRange::verify MAX_LEN (types.rs:448)
-
-// VoteRange::verify (types.rs:440-460), its checks in order: 1 = end < start, 2 = length
-// >= MAX_LEN, 3 = end >= MAX_LEN, 0 = valid
-MV_DEV uint32_t vr_code(uint64_t s0, uint64_t s1) {
-  return s1 < s0 ? 1u : (s1 - s0 >= VR_MAX_LEN ? 2u : (s1 >= VR_MAX_LEN ? 3u : 0u));
-}
-
-// 8 little-endian bytes at any address (the buffer is readable 16 bytes past every block)
-MV_DEV uint64_t peek8(const uint8_t* p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const uint64_t* w = reinterpret_cast<const uint64_t*>(a & ~static_cast<uintptr_t>(7));
-  const uint32_t sh = static_cast<uint32_t>(a & 7u) * 8u;
-  const uint64_t lo = w[0];
-  return sh ? (lo >> sh) | (w[1] << (64u - sh)) : lo;
-}
-
-// bincode reader over one block; every read is checked against the block's length
-struct BcReader {
-  const uint8_t* p;
-  uint64_t len, pos;
-  bool ok;
-  MV_DEV bool take(uint64_t k) {
-    if (!ok || k > len - pos) ok = false;
-    return ok;
-  }
-  MV_DEV uint64_t u64() {
-    if (!take(8)) return 0;
-    const uint64_t v = peek8(p + pos);
-    pos += 8;
-    return v;
-  }
-  MV_DEV uint32_t u32() {
-    if (!take(4)) return 0;
-    const uint32_t v = static_cast<uint32_t>(peek8(p + pos));
-    pos += 4;
-    return v;
-  }
-  MV_DEV uint32_t u8() {
-    if (!take(1)) return 0;
-    const uint32_t v = static_cast<uint32_t>(peek8(p + pos)) & 0xffu;
-    pos += 1;
-    return v;
-  }
-  // BlockReference: authority, round, digest (u64 length that must be 32, then 32 bytes)
-  MV_DEV void ref(uint64_t& a, uint64_t& r, const uint8_t*& d) {
-    a = u64();
-    r = u64();
-    const uint64_t l = u64();
-    if (ok && l != 32) ok = false;
-    d = p + pos;
-    if (take(32)) pos += 32;
-  }
-};
-
-// pre-image writer: bytes gathered into aligned 64-bit stores
-struct PreWriter {
+// pre-image writer: the walk's bytes as aligned 64-bit stores to the stage
+struct PreWriter : ByteGather<PreWriter> {
   uint64_t* out;
-  uint64_t acc;
-  uint32_t nb;  // bytes pending in acc (< 8)
-  uint64_t len;
-  // the k low bytes of v (1 <= k <= 8; the bytes of v above them are zero)
-  MV_DEV void put(uint64_t v, uint32_t k) {
-    acc |= v << (8 * nb);
-    const uint32_t t = nb + k;
-    if (t >= 8) {
-      *out++ = acc;
-      acc = nb ? v >> (64 - 8 * nb) : 0ull;
-      nb = t - 8;
-    } else {
-      nb = t;
-    }
-    len += k;
-  }
-  MV_DEV void be64(uint64_t x) { put(__builtin_bswap64(x), 8); }
-  MV_DEV void raw(const uint8_t* src, uint64_t k) {
-    for (; k >= 8; k -= 8, src += 8) put(peek8(src), 8);
-    if (k) put(peek8(src) & ((1ull << (8 * k)) - 1), static_cast<uint32_t>(k));
-  }
-  MV_DEV void ref(uint64_t a, uint64_t r, const uint8_t* d) {  // CryptoHash of BlockReference
-    be64(a);
-    be64(r);
-    raw(d, 32);
-  }
+  MV_DEV explicit PreWriter(uint64_t* o) : out(o) {}
+  MV_DEV void word(uint64_t w) { *out++ = w; }
   MV_DEV void flush() {
     if (nb) *out++ = acc;
     acc = 0;
@@ -112,138 +34,57 @@ struct IngestOut {
   uint32_t* facts;
   uint8_t* claimed;
 };
-struct CommitteeView {
-  const uint64_t* stakes;
-  uint32_t n_auth;
-  uint64_t epoch, quorum_thr;
-};
 
-// Block i = buf[o .. o + L), one lane, straight from global memory (no kernel of its own:
-// ingest_block calls it for a block over its LDS window). P || sig (then 8 zero
-// bytes) is written at stage + round_up(o, 8), which stays inside the block's own span
-// because the bincode is at least |P| + 128 bytes long; writes happen only after the bytes
-// they come from were read, so a malformed block never writes outside its span either.
-// seen[k * stride], k < 16: a zeroed authority bitmap (<= 512 authorities) for this lane.
-MV_DEV void ingest_lane(const uint8_t* buf, uint64_t o, uint64_t L, uint32_t i, const CommitteeView& cv,
-                        const IngestOut& io, uint32_t* seen, int stride) {
-  const uint32_t n_auth = cv.n_auth;
-  const uint64_t so = (o + 7) & ~7ull;
-  uint8_t* const stage = io.stage;
-  BcReader r{buf + o, L, 0, true};
-  PreWriter w{reinterpret_cast<uint64_t*>(stage + so), 0, 0, 0};
-
-  uint64_t me_a, me_r;
-  const uint8_t* me_d;
-  r.ref(me_a, me_r, me_d);
-  if (r.ok) {
-    w.be64(me_a);
-    w.be64(me_r);
+// What the verify ingest gathers on the walk: the include checks (types.rs:349-362), the
+// threshold clock's stake of the distinct round r-1 authorities (threshold_clock.rs:12-35), the
+// first failing VoteRange. seen[k * stride], k < 16: a zeroed authority bitmap (<= 512
+// authorities) for this lane.
+struct LaneChecks {
+  const CommitteeView& cv;
+  uint32_t* seen;
+  int stride;
+  uint64_t me_a = 0, me_r = 0, stake = 0, epoch = 0;
+  const uint8_t* me_d = nullptr;
+  uint32_t inc_err = 0, vr_first = 0;
+  MV_DEV void own(uint64_t a, uint64_t r, const uint8_t* d) {
+    me_a = a;
+    me_r = r;
+    me_d = d;
   }
-  // includes: pre-image, include checks (types.rs:349-362), threshold-clock stake
-  const uint64_t n_inc = r.u64();
-  uint32_t inc_err = 0;
-  uint64_t stake = 0;
-  bool quorum = false;
-  for (uint64_t k = 0; r.ok && k < n_inc; k++) {
-    uint64_t a, rd;
-    const uint8_t* d;
-    r.ref(a, rd, d);
-    if (!r.ok) break;
-    w.ref(a, rd, d);
-    if (inc_err == 0) {
-      if (a >= n_auth)
-        inc_err = MV_BLOCK_INCLUDE_UNKNOWN_AUTHORITY;
-      else if (rd >= me_r)
-        inc_err = MV_BLOCK_INCLUDE_ROUND;
-    }
-    if (me_r > 0 && rd == me_r - 1 && a < n_auth) {
+  MV_DEV void include(uint64_t a, uint64_t rd, const uint8_t*) {
+    if (inc_err == 0) inc_err = include_code(a, rd, me_r, cv.n_auth);
+    if (clock_include(a, rd, me_r, cv.n_auth)) {
       const uint32_t wd = static_cast<uint32_t>(a) >> 5, bit = 1u << (a & 31);
       const uint32_t s = seen[wd * stride];
       if (!(s & bit)) {
         seen[wd * stride] = s | bit;
         stake += cv.stakes[a];
       }
-      quorum = stake > cv.quorum_thr;
     }
   }
-  // statements
-  const uint64_t n_st = r.u64();
-  uint32_t vr_first = 0;
-  for (uint64_t k = 0; r.ok && k < n_st; k++) {
-    const uint32_t tag = r.u32();
-    if (!r.ok) break;
-    if (tag == 0) {  // Share(Transaction): raw bytes, no length in the pre-image
-      const uint64_t l = r.u64();
-      if (!r.take(l)) break;
-      w.put(0, 1);
-      w.raw(r.p + r.pos, l);
-      r.pos += l;
-    } else if (tag == 1) {  // Vote(TransactionLocator, Vote)
-      uint64_t a, rd;
-      const uint8_t* d;
-      r.ref(a, rd, d);
-      const uint64_t lo = r.u64();
-      const uint32_t vote = r.u32();
-      if (!r.ok) break;
-      if (vote == 0) {  // Accept
-        w.put(1, 1);
-        w.ref(a, rd, d);
-        w.be64(lo);
-      } else if (vote == 1) {  // Reject(Option<TransactionLocator>)
-        const uint32_t some = r.u8();
-        if (!r.ok) break;
-        if (some == 0) {
-          w.put(2, 1);
-          w.ref(a, rd, d);
-          w.be64(lo);
-        } else if (some == 1) {
-          uint64_t a2, rd2;
-          const uint8_t* d2;
-          r.ref(a2, rd2, d2);
-          const uint64_t lo2 = r.u64();
-          if (!r.ok) break;
-          w.put(3, 1);
-          w.ref(a, rd, d);
-          w.be64(lo);
-          w.ref(a2, rd2, d2);
-          w.be64(lo2);
-        } else {
-          r.ok = false;
-        }
-      } else {
-        r.ok = false;
-      }
-    } else if (tag == 2) {  // VoteRange(TransactionLocatorRange)
-      uint64_t a, rd;
-      const uint8_t* d;
-      r.ref(a, rd, d);
-      const uint64_t s0 = r.u64(), s1 = r.u64();
-      if (!r.ok) break;
-      w.put(4, 1);
-      w.ref(a, rd, d);
-      w.be64(s0);
-      w.be64(s1);
-      if (!vr_first) vr_first = vr_code(s0, s1);
-    } else {
-      r.ok = false;
-    }
+  MV_DEV void vote_range(uint64_t s0, uint64_t s1) {
+    if (!vr_first) vr_first = vr_code(s0, s1);
   }
-  // meta_creation_time_ns (u128), epoch_marker (bool), epoch, signature
-  const uint64_t tlo = r.u64(), thi = r.u64();
-  const uint32_t marker = r.u8();
-  if (r.ok && marker > 1) r.ok = false;
-  const uint64_t ep = r.u64();
-  const uint64_t sl = r.u64();
-  if (r.ok && sl != 64) r.ok = false;
-  const uint8_t* sp = r.p + r.pos;
-  const bool parsed = r.take(64);
+  MV_DEV void meta(uint64_t ep, uint64_t) { epoch = ep; }
+};
+
+// Block i = buf[o .. o + L), one lane, straight from global memory (no kernel of its own:
+// ingest_block calls it for a block over its LDS window): the shared walk (bincode_walk.h) under
+// the verify checks. P || sig (then 8 zero bytes) is written at stage + round_up(o, 8), which
+// stays inside the block's own span because the bincode is at least |P| + 128 bytes long; writes
+// happen only after the bytes they come from were read, so a malformed block never writes outside
+// its span either. The buffer is readable 16 bytes past every block.
+MV_DEV void ingest_lane(const uint8_t* buf, uint64_t o, uint64_t L, uint32_t i, const CommitteeView& cv,
+                        const IngestOut& io, uint32_t* seen, int stride) {
+  const uint64_t so = (o + 7) & ~7ull;
+  BcReader r{buf + o, L, 0, true};
+  PreWriter w(reinterpret_cast<uint64_t*>(io.stage + so));
+  LaneChecks c{cv, seen, stride};
+  const bool parsed = block_walk(r, w, c);
   uint32_t sw[16];
   uint32_t f = 0;
   if (parsed) {
-    w.be64(thi);
-    w.be64(tlo);
-    w.put(marker, 1);
-    w.be64(ep);
+    const uint8_t* sp = r.p + r.pos;
     const uint64_t plen = w.len;
 #pragma unroll
     for (int q = 0; q < 8; q++) {
@@ -255,31 +96,16 @@ MV_DEV void ingest_lane(const uint8_t* buf, uint64_t o, uint64_t L, uint32_t i, 
     w.put(0, 8);  // a zero word after P || sig
     w.flush();
     io.pre_len[i] = plen;
-    f = BF_PARSED | (ep == cv.epoch ? BF_EPOCH_OK : 0u) | (me_a < n_auth ? BF_AUTHOR_OK : 0u) |
-        (me_r == 0 ? BF_GENESIS : 0u) | (vr_first << BF_VR_SHIFT) | (quorum ? BF_QUORUM : 0u) |
-        (inc_err << BF_INC_SHIFT);
-    const uint64_t d0 = peek8(me_d), d1 = peek8(me_d + 8), d2 = peek8(me_d + 16), d3 = peek8(me_d + 24);
-    uint4* cd = reinterpret_cast<uint4*>(io.claimed + 32 * (size_t)i);
-    cd[0] = make_uint4((uint32_t)d0, (uint32_t)(d0 >> 32), (uint32_t)d1, (uint32_t)(d1 >> 32));
-    cd[1] = make_uint4((uint32_t)d2, (uint32_t)(d2 >> 32), (uint32_t)d3, (uint32_t)(d3 >> 32));
+    f = block_facts(c.epoch == cv.epoch, c.me_a < cv.n_auth, c.me_r == 0, c.vr_first, c.stake > cv.quorum_thr,
+                    c.inc_err);
   } else {
     io.pre_len[i] = 0;
 #pragma unroll
     for (int q = 0; q < 16; q++) sw[q] = 0;
   }
   io.pre_off[i] = so;
-  // a block rejected ahead of the signature check gets s = 2^256 - 1 (>= l): its verdict
-  // does not depend on the signature, and s >= l keeps it out of the batch equation
-  const bool sig_decides = parsed && (f & BF_EPOCH_OK) && (f & BF_AUTHOR_OK) && !(f & BF_GENESIS);
-  if (!sig_decides) {
-#pragma unroll
-    for (int q = 8; q < 16; q++) sw[q] = 0xffffffffu;
-  }
-  uint4* so4 = reinterpret_cast<uint4*>(io.sig_out + 64 * (size_t)i);
-#pragma unroll
-  for (int q = 0; q < 4; q++) so4[q] = make_uint4(sw[4 * q], sw[4 * q + 1], sw[4 * q + 2], sw[4 * q + 3]);
-  io.key_idx[i] = (parsed && me_a < n_auth) ? static_cast<uint32_t>(me_a) : 0u;
-  io.facts[i] = f;
+  store_block_outputs(i, f, static_cast<uint32_t>(c.me_a), sw, [&](int q) { return peek8(c.me_d + 8 * q); },
+                      io.sig_out, io.claimed, io.key_idx, io.facts);
 }
 
 // ---------------------------------------------------------------- wave per block
@@ -288,8 +114,8 @@ MV_DEV void ingest_lane(const uint8_t* buf, uint64_t o, uint64_t L, uint32_t i, 
 // variable-size statements are located 64 at a time by lane 0 walking their headers, then
 // transcoded one per lane (Share payloads copied by the whole wave); the pre-image is built
 // in LDS and written to the stage with coalesced stores. Blocks that do not fit the LDS
-// window take the one-lane function ingest_lane on lane 0. The rules are ingest_lane's (and
-// block_codec.cpp's); tests/test_gpu_ingest.py holds every ingest form and the host codec to
+// window take the one-lane function ingest_lane on lane 0. The rules are the shared walk's
+// (bincode_walk.h), block_verdict.h's and block_codec.cpp's; tests/test_gpu_ingest.py holds every ingest form and the host codec to
 // identical results.
 constexpr uint32_t IG_WIN = 10240;  // LDS window per block, bytes
 constexpr uint32_t IG_CHUNK = 64;   // statements located per walk
@@ -445,9 +271,9 @@ MV_DEV void ingest_block(uint32_t i, const uint8_t* __restrict__ buf, const uint
       pq[1] = __builtin_bswap64(r);
 #pragma unroll
       for (int m = 0; m < 4; m++) pq[2 + m] = dg[m];
-      const uint32_t code = a >= n_auth ? MV_BLOCK_INCLUDE_UNKNOWN_AUTHORITY : (r >= me_r ? MV_BLOCK_INCLUDE_ROUND : 0u);
+      const uint32_t code = include_code(a, r, me_r, n_auth);
       if (code && inc_first == 0xffffffffu) inc_first = (k << 4) | code;
-      if (me_r > 0 && r == me_r - 1 && a < n_auth) atomicOr(&seen[(uint32_t)a >> 5], 1u << (a & 31));
+      if (clock_include(a, r, me_r, n_auth)) atomicOr(&seen[(uint32_t)a >> 5], 1u << (a & 31));
     }
   }
   inc_first = wave_min(inc_first);
@@ -642,9 +468,7 @@ MV_DEV void ingest_block(uint32_t i, const uint8_t* __restrict__ buf, const uint
     const uint32_t inc_code = inc_first == 0xffffffffu ? 0u : (inc_first & 15u);
     vr_first = wave_min(vr_first);
     const uint32_t vr = vr_first == 0xffffffffu ? 0u : (vr_first & 3u);
-    f = BF_PARSED | (ep == cv.epoch ? BF_EPOCH_OK : 0u) | (me_a < n_auth ? BF_AUTHOR_OK : 0u) |
-        (me_r == 0 ? BF_GENESIS : 0u) | (vr << BF_VR_SHIFT) | (stake > cv.quorum_thr ? BF_QUORUM : 0u) |
-        (inc_code << BF_INC_SHIFT);
+    f = block_facts(ep == cv.epoch, me_a < n_auth, me_r == 0, vr, stake > cv.quorum_thr, inc_code);
   }
   ig_sync<WAVE>();
   const uint64_t so = (o + 7) & ~7ull;
@@ -661,15 +485,8 @@ MV_DEV void ingest_block(uint32_t i, const uint8_t* __restrict__ buf, const uint
     uint32_t sw[16];  // the signature, from its pre-image copy (its bincode was overwritten)
 #pragma unroll
     for (int q = 0; q < 16; q++) sw[q] = ok ? lds_u32(win, plen + 4 * q) : 0u;
-    const bool sig_decides = ok && (f & BF_EPOCH_OK) && (f & BF_AUTHOR_OK) && !(f & BF_GENESIS);
-    if (!sig_decides) {
-#pragma unroll
-      for (int q = 8; q < 16; q++) sw[q] = 0xffffffffu;
-    }
-    uint4* so4 = reinterpret_cast<uint4*>(io.sig_out + 64 * (size_t)i);
-#pragma unroll
-    for (int q = 0; q < 4; q++) so4[q] = make_uint4(sw[4 * q], sw[4 * q + 1], sw[4 * q + 2], sw[4 * q + 3]);
-    io.key_idx[i] = (ok && me_a < n_auth) ? (uint32_t)me_a : 0u;
+    store_sig(io.sig_out, i, sw, f);
+    io.key_idx[i] = block_key(f, (uint32_t)me_a);
     io.facts[i] = f;
   }
 }

@@ -296,47 +296,11 @@ __global__ void __launch_bounds__(256, 2)
   lds_btab_load(btab, btab_g, BT_TABLE);
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t idx = gid < n ? gid : n - 1;
-  uint32_t sw[8], mw[8], h[16];
+  uint32_t sw[8], mw[8], ared[8], prefix[8], pkw[8], Rw[8], S[8];
   load8(sw, seed + 32 * (size_t)idx);
   load8(mw, msg + 32 * (size_t)idx);
-  sha512_short(h, sw, 32);
-  uint32_t a[16];
-#pragma unroll
-  for (int i = 0; i < 8; i++) a[i] = h[i];
-  a[0] &= 0xfffffff8u;
-  a[7] = (a[7] & 0x7fffffffu) | 0x40000000u;
-#pragma unroll
-  for (int i = 8; i < 16; i++) a[i] = 0;
-  uint32_t ared[8], sd[8];
-  sc_reduce512(ared, a);  // [a]B == [a mod l]B keeps the top digit in range
-  sc_recode256(sd, ared);
-  p3 P;
-  basemul(P, sd, btab);
-  uint32_t pkw[8];
-  p3_compress(pkw, P);
-  // r = SHA-512(prefix || M) mod l
-  uint32_t rin[16], rh[16], r[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    rin[i] = h[8 + i];
-    rin[8 + i] = mw[i];
-  }
-  sha512_short(rh, rin, 64);
-  sc_reduce512(r, rh);
-  sc_recode256(sd, r);
-  basemul(P, sd, btab);
-  uint32_t Rw[8];
-  p3_compress(Rw, P);
-  uint32_t kin[24], kh[16], k[8], S[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    kin[i] = Rw[i];
-    kin[8 + i] = pkw[i];
-    kin[16 + i] = mw[i];
-  }
-  sha512_short(kh, kin, 96);
-  sc_reduce512(k, kh);
-  sc_muladd(S, k, ared, r);
+  ed25519_expand(ared, prefix, pkw, sw, btab);
+  ed25519_sign(Rw, S, ared, prefix, pkw, mw, btab);
   if (gid < n) {
     store8(pk_out + 32 * (size_t)gid, pkw);
     store8(sig_out + 64 * (size_t)gid, Rw);

@@ -17,22 +17,17 @@
 // block of P and its unfinished tail; B2(P) finalises a copy, the signature is then appended to
 // the original and finalised as B2(P || sig). Nothing of P is hashed twice.
 //
-// Every offset read from the bincode passes BcReader::take (ingest_dev.h) against the block's
-// length before it becomes an address, and off + len is held against the buffer's size first.
-// Reads are whole aligned 8-byte words that cover a checked range: they stay inside the 8-byte
-// aligned buffer padded by 8 bytes. Stores go to the include digests (linked calls), the own
+// The walk and its memory-safety argument are bincode_walk.h's; off + len is held against the
+// buffer's size before it (block_span). Stores go to the include digests (linked calls), the own
 // digest (bytes 24..56) and the signature (the 64 bytes the walk ends on) of a block that passed
 // k_seal_scan, and nowhere else in the buffer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/mysti_verify.h"
-#include "fe25519.h"
-#include "ge25519.h"
-#include "hash_dev.h"
-#include "ingest_dev.h"
+#include "bincode_walk.h"
+#include "blake2b_quad.h"
 #include "kernels.h"
-#include "scalar25519.h"
 #include "tables.h"
 
 namespace mv {
@@ -66,178 +61,65 @@ MV_DEV void poke8(uint8_t* p, uint64_t v) { __builtin_memcpy(p, &v, 8); }
 // BLAKE2b-256 over bytes as they are produced. The lane's 128-byte message block lives in LDS,
 // word w of lane l at row[64 w + l] (no two lanes of a wave share a bank); a full block is
 // compressed only when the next word arrives, so the last block is always still in the row.
-struct B2Stream {
+struct B2Stream : ByteGather<B2Stream> {
   uint64_t h[8];
   uint64_t* row;
-  uint64_t acc, total;
-  uint32_t nw, nb;  // whole words in the row (<= 16), bytes pending in acc (< 8)
+  uint32_t nw = 0;  // whole words in the row (<= 16)
 
-  MV_DEV void init(uint64_t* lane_row) {
-    b2_init256(h);
-    row = lane_row;
-    acc = total = 0;
-    nw = nb = 0;
-  }
-  MV_DEV void load(uint64_t m[16], uint32_t words, uint64_t tail) const {
+  MV_DEV explicit B2Stream(uint64_t* lane_row) : row(lane_row) { b2q::lane_init256(h); }
+  MV_DEV void load(uint64_t (&m)[16], uint32_t words, uint64_t tail) const {
 #pragma unroll
     for (uint32_t j = 0; j < 16; j++) m[j] = j < words ? row[64 * j] : (j == words ? tail : 0ull);
   }
-  MV_DEV void push(uint64_t w) {
+  MV_DEV void word(uint64_t w) {
     if (nw == 16) {
       uint64_t m[16];
       load(m, 16, 0);
-      b2_compress(h, m, total - nb, false);  // the bytes in whole words so far (put() calls before it counts)
+      b2q::lane_compress(h, m, len - nb, false);  // the bytes in whole words so far (put() counts after word())
       nw = 0;
     }
     row[64 * nw++] = w;
   }
-  // the k low bytes of v (1 <= k <= 8; the bytes of v above them are zero)
-  MV_DEV void put(uint64_t v, uint32_t k) {
-    const uint64_t full = acc | (v << (8 * nb));
-    const uint32_t t = nb + k;
-    if (t >= 8) {
-      push(full);  // (before nb and total move: push reads them)
-      acc = nb ? v >> (64 - 8 * nb) : 0ull;
-      nb = t - 8;
-    } else {
-      acc = full;
-      nb = t;
-    }
-    total += k;
-  }
-  MV_DEV void be64(uint64_t x) { put(__builtin_bswap64(x), 8); }
-  MV_DEV void raw(const uint8_t* src, uint64_t k) {
-    for (; k >= 8; k -= 8, src += 8) put(peek8(src), 8);
-    if (k) put(peek8(src) & ((1ull << (8 * k)) - 1), (uint32_t)k);
-  }
   // the digest of the bytes so far; the stream goes on unchanged
-  MV_DEV void digest(uint64_t out[4]) const {
+  MV_DEV void digest(uint64_t (&out)[4]) const {
     uint64_t hc[8], m[16];
 #pragma unroll
     for (int j = 0; j < 8; j++) hc[j] = h[j];
     if (nw == 16 && nb) {  // a full block, then the tail bytes in a block of their own
       load(m, 16, 0);
-      b2_compress(hc, m, total - nb, false);
+      b2q::lane_compress(hc, m, len - nb, false);
       load(m, 0, acc);
     } else {
       load(m, nw, acc);
     }
-    b2_compress(hc, m, total, true);
+    b2q::lane_compress(hc, m, len, true);
 #pragma unroll
     for (int j = 0; j < 4; j++) out[j] = hc[j];
   }
 };
 
-// Sink of the walk that only parses (k_seal_scan).
-struct NoSink {
-  MV_DEV void put(uint64_t, uint32_t) {}
-  MV_DEV void be64(uint64_t) {}
-  MV_DEV void raw(const uint8_t*, uint64_t) {}
-};
-
-struct Head {
-  uint64_t author, round;
-  uint32_t sig_pos;  // of the 64 signature bytes in the block
-};
-
-// The walk of one block (ingest_lane's, without the verify checks): the pre-image goes to `w`
-// piece by piece. inc(a, r, d): called per include before its digest bytes at d are read.
-// Returns false on any bincode error.
-template <class Sink, class IncFn>
-MV_DEV bool walk(BcReader& r, Sink& w, Head& hd, IncFn inc) {
-  uint64_t me_a, me_r;
-  const uint8_t* me_d;
-  r.ref(me_a, me_r, me_d);
-  if (!r.ok) return false;
-  hd.author = me_a;
-  hd.round = me_r;
-  w.be64(me_a);
-  w.be64(me_r);
-  const uint64_t n_inc = r.u64();
-  if (r.ok && n_inc > (r.len - r.pos) / 56) r.ok = false;
-  for (uint64_t k = 0; r.ok && k < n_inc; k++) {
-    uint64_t a, rd;
-    const uint8_t* d;
-    r.ref(a, rd, d);
-    if (!r.ok) break;
-    inc(a, rd, const_cast<uint8_t*>(d));
-    w.be64(a);
-    w.be64(rd);
-    w.raw(d, 32);
+// What sealing takes from the walk: the block's (authority, round), where its signature lies, and
+// link(a, r, d), called per include before its digest bytes at d are read.
+template <class LinkFn>
+struct SealVisitor {
+  LinkFn link;
+  uint64_t author = 0, round = 0;
+  uint32_t sig_pos = 0;  // of the 64 signature bytes in the block
+  bool fits = false;     // sig_pos holds the position
+  MV_DEV void own(uint64_t a, uint64_t r, const uint8_t*) {
+    author = a;
+    round = r;
   }
-  const uint64_t n_st = r.u64();
-  if (r.ok && n_st > (r.len - r.pos) / 12) r.ok = false;
-  for (uint64_t k = 0; r.ok && k < n_st; k++) {
-    const uint32_t tag = r.u32();
-    if (!r.ok) break;
-    if (tag == 0) {  // Share(Transaction): 0x00, raw bytes
-      const uint64_t l = r.u64();
-      if (!r.take(l)) break;
-      w.put(0, 1);
-      w.raw(r.p + r.pos, l);
-      r.pos += l;
-    } else if (tag == 1) {  // Vote(TransactionLocator, Vote)
-      uint64_t a, rd;
-      const uint8_t* d;
-      r.ref(a, rd, d);
-      const uint64_t lo = r.u64();
-      const uint32_t vote = r.u32();
-      if (!r.ok) break;
-      if (vote == 0) {
-        w.put(1, 1);
-        w.be64(a), w.be64(rd), w.raw(d, 32);
-        w.be64(lo);
-      } else if (vote == 1) {
-        const uint32_t some = r.u8();
-        if (!r.ok) break;
-        if (some == 0) {
-          w.put(2, 1);
-          w.be64(a), w.be64(rd), w.raw(d, 32);
-          w.be64(lo);
-        } else if (some == 1) {
-          uint64_t a2, rd2;
-          const uint8_t* d2;
-          r.ref(a2, rd2, d2);
-          const uint64_t lo2 = r.u64();
-          if (!r.ok) break;
-          w.put(3, 1);
-          w.be64(a), w.be64(rd), w.raw(d, 32);
-          w.be64(lo);
-          w.be64(a2), w.be64(rd2), w.raw(d2, 32);
-          w.be64(lo2);
-        } else {
-          r.ok = false;
-        }
-      } else {
-        r.ok = false;
-      }
-    } else if (tag == 2) {  // VoteRange
-      uint64_t a, rd;
-      const uint8_t* d;
-      r.ref(a, rd, d);
-      const uint64_t s0 = r.u64(), s1 = r.u64();
-      if (!r.ok) break;
-      w.put(4, 1);
-      w.be64(a), w.be64(rd), w.raw(d, 32);
-      w.be64(s0);
-      w.be64(s1);
-    } else {
-      r.ok = false;
-    }
+  MV_DEV void include(uint64_t a, uint64_t r, const uint8_t* d) { link(a, r, const_cast<uint8_t*>(d)); }
+  MV_DEV void vote_range(uint64_t, uint64_t) {}
+  MV_DEV void meta(uint64_t, uint64_t pos) {
+    fits = pos <= 0xffffff00ull;
+    sig_pos = (uint32_t)pos;
   }
-  const uint64_t tlo = r.u64(), thi = r.u64();
-  const uint32_t marker = r.u8();
-  if (r.ok && marker > 1) r.ok = false;
-  const uint64_t ep = r.u64();
-  const uint64_t sl = r.u64();
-  if (r.ok && sl != 64) r.ok = false;
-  if (!r.take(64) || r.pos > 0xffffff00ull) return false;
-  hd.sig_pos = (uint32_t)r.pos;
-  w.be64(thi);
-  w.be64(tlo);
-  w.put(marker, 1);
-  w.be64(ep);
-  return true;
+};
+template <class Sink, class LinkFn>
+MV_DEV bool seal_walk(BcReader& r, Sink& w, SealVisitor<LinkFn>& vis) {
+  return block_walk(r, w, vis) && vis.fits;
 }
 
 // Where block i lies, or false when its span leaves the buffer.
@@ -254,27 +136,15 @@ __global__ void __launch_bounds__(64) k_seal_keys(const uint8_t* __restrict__ se
   lds_btab_load(btab, btab_g, BT_TABLE);
   const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= n_auth) return;
-  uint32_t sw[8], h[16];
+  uint32_t sw[8], ared[8], prefix[8], pkw[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) sw[i] = reinterpret_cast<const uint32_t*>(seeds)[8 * (size_t)a + i];
-  sha512_short(h, sw, 32);
-  uint32_t s[16], ared[8], sd[8], pkw[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) s[i] = h[i];
-  s[0] &= 0xfffffff8u;
-  s[7] = (s[7] & 0x7fffffffu) | 0x40000000u;
-#pragma unroll
-  for (int i = 8; i < 16; i++) s[i] = 0;
-  sc_reduce512(ared, s);  // [a]B == [a mod l]B, and S = r + k a mod l takes a mod l
-  sc_recode256(sd, ared);
-  p3 P;
-  basemul(P, sd, btab);
-  p3_compress(pkw, P);
+  ed25519_expand(ared, prefix, pkw, sw, btab);
   uint32_t* o = keys + KEY_WORDS * (size_t)a;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     o[i] = ared[i];
-    o[8 + i] = h[8 + i];
+    o[8 + i] = prefix[i];
     o[16 + i] = pkw[i];
   }
 }
@@ -286,12 +156,13 @@ __global__ void __launch_bounds__(256) k_seal_scan(const uint8_t* __restrict__ b
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint64_t o, L;
-  Head hd{0, 0, 0};
+  auto no_link = [](uint64_t, uint64_t, uint8_t*) {};
+  SealVisitor<decltype(no_link)> hd{no_link};
   bool ok = block_span(off, len, i, buf_bytes, o, L);
   if (ok) {
     BcReader r{buf + o, L, 0, true};
     NoSink ns;
-    ok = walk(r, ns, hd, [](uint64_t, uint64_t, uint8_t*) {});
+    ok = seal_walk(r, ns, hd);
   }
   status[i] = !ok ? MV_SEAL_PARSE_ERROR : (hd.author >= n_auth ? MV_SEAL_UNKNOWN_AUTHOR : MV_SEAL_OK);
   heads[2 * (size_t)i] = ok ? hd.author : ~0ull;
@@ -334,12 +205,10 @@ __global__ void __launch_bounds__(64 * WAVES)
     }
   }
 
-  B2Stream st;
-  st.init(&rows[threadIdx.x >> 6][threadIdx.x & 63]);
+  B2Stream st(&rows[threadIdx.x >> 6][threadIdx.x & 63]);
   BcReader r{blk, L, 0, true};
-  Head hd{0, 0, 0};
   const uint64_t my_round = peek8(blk + 8);
-  const bool ok = walk(r, st, hd, [&](uint64_t a, uint64_t rd, uint8_t* d) {
+  auto link = [&](uint64_t a, uint64_t rd, uint8_t* d) {
     if (!tab.slots || rd >= my_round) return;
     const uint32_t j = tab_find(tab, a, rd);
     // a matched block that was itself left unlinked has no fresh digest: the bytes stay
@@ -347,7 +216,9 @@ __global__ void __launch_bounds__(64 * WAVES)
     const uint64_t* dg = reinterpret_cast<const uint64_t*>(bd_all + 32 * (size_t)j);
 #pragma unroll
     for (int q = 0; q < 4; q++) poke8(d + 8 * q, dg[q]);
-  });
+  };
+  SealVisitor<decltype(link)> hd{link};
+  const bool ok = seal_walk(r, st, hd);
   if (!ok) {  // cannot happen after k_seal_scan: the walk is the same and the link changes no length
     status[i] = MV_SEAL_PARSE_ERROR;
     return;
@@ -361,32 +232,15 @@ __global__ void __launch_bounds__(64 * WAVES)
     mw[2 * q] = (uint32_t)m64[q];
     mw[2 * q + 1] = (uint32_t)(m64[q] >> 32);
   }
-  // RFC 8032 5.1.6 with the expanded key: r = H(prefix || m) mod l, R = [r]B,
-  // S = r + H(R || A || m) a mod l
   const uint32_t* key = keys + KEY_WORDS * (size_t)hd.author;  // author < n_auth: status is OK
-  uint32_t ared[8], rin[16], rh[16], rr[8], sd[8], Rw[8];
+  uint32_t ared[8], prefix[8], pkw[8], Rw[8], S[8];
 #pragma unroll
   for (int q = 0; q < 8; q++) {
     ared[q] = key[q];
-    rin[q] = key[8 + q];
-    rin[8 + q] = mw[q];
+    prefix[q] = key[8 + q];
+    pkw[q] = key[16 + q];
   }
-  sha512_short(rh, rin, 64);
-  sc_reduce512(rr, rh);
-  sc_recode256(sd, rr);
-  p3 P;
-  basemul(P, sd, btab);
-  p3_compress(Rw, P);
-  uint32_t kin[24], kh[16], kk[8], S[8];
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    kin[q] = Rw[q];
-    kin[8 + q] = key[16 + q];
-    kin[16 + q] = mw[q];
-  }
-  sha512_short(kh, kin, 96);
-  sc_reduce512(kk, kh);
-  sc_muladd(S, kk, ared, rr);
+  ed25519_sign(Rw, S, ared, prefix, pkw, mw, btab);
 
   uint64_t sg[8];
 #pragma unroll
@@ -399,7 +253,7 @@ __global__ void __launch_bounds__(64 * WAVES)
   uint64_t d64[4];
   st.digest(d64);  // d = B2(P || sig)
 
-  uint8_t* sp = blk + hd.sig_pos;  // sig_pos + 64 <= L: walk() took the 64 bytes
+  uint8_t* sp = blk + hd.sig_pos;  // sig_pos + 64 <= L: the walk checked the 64 bytes
 #pragma unroll
   for (int q = 0; q < 8; q++) poke8(sp + 8 * q, sg[q]);
 #pragma unroll

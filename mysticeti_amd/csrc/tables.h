@@ -5,6 +5,7 @@
 #pragma once
 #include "fe25519.h"
 #include "ge25519.h"
+#include "hash_dev.h"
 #include "scalar25519.h"
 
 namespace mv {
@@ -139,6 +140,54 @@ MV_DEV void basemul(p3& out, const uint32_t sd[8], const uint4* btab) {
     if (w != 0) p1p1_to_p2(P, Q);
   }
   p1p1_to_p3(out, Q);
+}
+
+// RFC 8032 5.1.5: seed -> the expanded key (a mod l, prefix) and the compressed public key [a]B.
+// [a]B == [a mod l]B keeps basemul's top digit in range, and S = r + k a mod l takes a mod l.
+MV_DEV void ed25519_expand(uint32_t (&ared)[8], uint32_t (&prefix)[8], uint32_t (&pkw)[8], const uint32_t (&seed)[8],
+                           const uint4* btab) {
+  uint32_t h[16], a[16], sd[8];
+  sha512_short(h, seed, 32);
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    a[i] = h[i];
+    a[8 + i] = 0;
+    prefix[i] = h[8 + i];
+  }
+  a[0] &= 0xfffffff8u;
+  a[7] = (a[7] & 0x7fffffffu) | 0x40000000u;
+  sc_reduce512(ared, a);
+  sc_recode256(sd, ared);
+  p3 P;
+  basemul(P, sd, btab);
+  p3_compress(pkw, P);
+}
+// RFC 8032 5.1.6 with the expanded key, on a 32-byte message: r = H(prefix || m) mod l, R = [r]B,
+// S = r + H(R || A || m) a mod l
+MV_DEV void ed25519_sign(uint32_t (&Rw)[8], uint32_t (&S)[8], const uint32_t (&ared)[8], const uint32_t (&prefix)[8],
+                         const uint32_t (&pkw)[8], const uint32_t (&mw)[8], const uint4* btab) {
+  uint32_t rin[16], rh[16], r[8], sd[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    rin[i] = prefix[i];
+    rin[8 + i] = mw[i];
+  }
+  sha512_short(rh, rin, 64);
+  sc_reduce512(r, rh);
+  sc_recode256(sd, r);
+  p3 P;
+  basemul(P, sd, btab);
+  p3_compress(Rw, P);
+  uint32_t kin[24], kh[16], k[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    kin[i] = Rw[i];
+    kin[8 + i] = pkw[i];
+    kin[16 + i] = mw[i];
+  }
+  sha512_short(kh, kin, 96);
+  sc_reduce512(k, kh);
+  sc_muladd(S, k, ared, r);
 }
 
 MV_DEV void quads_to_precomp(precomp& p, const uint4 (&q)[7]) {

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import blocks as B
+import lane_kinds as K
 import mysticeti_amd as M
 import oracle as O
 
@@ -244,3 +245,19 @@ def test_blocks_beyond_the_lds_window(engine, host_engine):
         if ost != O.BLOCK_PARSE_ERROR:
             assert md[i].tobytes() == omd and bd[i].tobytes() == obd, i
     assert int(st[-3]) == M.BLOCK_DIGEST_MISMATCH and int(st[-2]) == M.BLOCK_PARSE_ERROR
+
+
+def test_one_lane_walk_every_statement_kind(engine, host_engine):
+    """Blocks just over the LDS window (tests/lane_kinds.py), so the one-lane walk reads them: a Share
+    of ~10.3 KB followed by a Vote Accept, Reject(None), Reject(Some), a VoteRange or nothing, and
+    five malformed in the Vote branches (vote tag 2, option byte 2, statement tag 3, a Reject(Some)
+    cut inside its second locator, a second locator's digest length 31). Every form agrees with the
+    host codec; every status is the oracle's, and every digest where the oracle parses."""
+    bins, names = K.corpus()
+    pks, stakes, epoch = K.committee()
+    st, md, bd = agree(engine, host_engine, list(bins), pks, stakes, epoch)
+    for i, (ost, omd, obd) in enumerate(K.oracle_results()):
+        assert int(st[i]) == ost, names[i]
+        if ost != O.BLOCK_PARSE_ERROR:
+            assert md[i].tobytes() == omd and bd[i].tobytes() == obd, names[i]
+    assert [int(s) for s in st] == [M.BLOCK_OK] * 11 + [M.BLOCK_PARSE_ERROR] * 5

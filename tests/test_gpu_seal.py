@@ -232,3 +232,46 @@ def test_device_variant(engine, corpus):
     torch.cuda.synchronize()
     engine.dev_seal_blocks(0, d_buf2, len(raw) - 16, d_off, d_len, d_seeds, d_st, link=False)
     assert d_buf2.cpu().numpy().tobytes() == hbuf.tobytes() and np.array_equal(d_st.cpu().numpy(), hst)
+
+
+def test_seal_signs_as_ed25519_sign(engine):
+    """8. Seal and sign share one signer: five blocks of seal_cases, one per authority; the 64
+    signature bytes seal_blocks leaves in each block are ed25519_sign(seed[a], md[i])'s. The key rows
+    (a mod l, prefix, public key) stay on the device, so their public keys are held to that call's pk
+    through what they feed: the challenge H(R || A || m) inside the equal signature, which also
+    verifies under pk."""
+    seeds = C.seeds()
+    g = BL.genesis_refs(C.N_AUTH)
+    blocks = [C.blk(a, 1, [g[a]], n_extra=a) for a in range(C.N_AUTH)]
+    buf, offs, lens, st, md, bd = gpu_seal(engine, blocks, seeds, False)
+    assert st.tolist() == [M.SEAL_OK] * C.N_AUTH
+    pk, sig = engine.ed25519_sign(seed_rows(seeds), md)
+    for i in range(C.N_AUTH):
+        assert buf[offs[i] + lens[i] - 64:offs[i] + lens[i]].tobytes() == sig[i].tobytes(), i
+    assert engine.ed25519_verify(md, sig, pk=pk).tolist() == [M.SIG_OK] * C.N_AUTH
+    assert len({p.tobytes() for p in pk}) == C.N_AUTH
+
+
+@pytest.mark.parametrize("n", [64, M.BATCH_MIN])
+def test_seal_stream_equals_the_hash_kernels(engine, n):
+    """9. The seal stream and the hash kernels share one compression: over the tail_sweep family of
+    tests/preimage_edges.py (|P| % 128 through every value, every tail kind), seal_blocks' md is
+    Engine.blake2b256 of the model's pre-image and bd of pre-image || signature -- the four-lane hash
+    at 64 strings, the one-lane hash at MV_BATCH_MIN."""
+    sweep = PE.family("tail_sweep")
+    if n < len(sweep):  # the tails in turn, |P| % 128 at the schedule's edges and at the even values between
+        want = list(PE.RESIDUES) + [r for r in range(2, 127, 2) if r != 64][:n - len(PE.RESIDUES)]
+        cases = [next(c for c in sweep if c.tail == PE.TAILS[i % 5] and len(c.block.preimage()) % 128 == r)
+                 for i, r in enumerate(want)]
+    else:
+        cases = [sweep[i % len(sweep)] for i in range(n)]
+    assert len(cases) == n and {c.tail for c in cases} == set(PE.TAILS)
+    assert set(PE.RESIDUES) <= {len(c.block.preimage()) % 128 for c in cases}
+    seeds = [BL.authority_seed(a) for a in range(PE.N_AUTH)]
+    buf, offs, lens, st, md, bd = gpu_seal(engine, [c.bincode for c in cases], seeds, False)
+    assert st.tolist() == [M.SEAL_OK] * n
+    pre = [c.block.preimage() for c in cases]
+    sigs = [buf[offs[i] + lens[i] - 64:offs[i] + lens[i]].tobytes() for i in range(n)]
+    assert sigs == [c.block.signature for c in cases]
+    assert [x.tobytes() for x in md] == engine.blake2b256(pre)
+    assert [x.tobytes() for x in bd] == engine.blake2b256([p + s for p, s in zip(pre, sigs)])
