@@ -893,7 +893,8 @@ mv_status mv_set_option(mv_ctx* ctx, const char* name, int64_t value);
 mv_status mv_get_option(mv_ctx* ctx, const char* name, int64_t* value);
 /* Runs field/scalar primitive `op` on n lane inputs (16 words each) -> 16 words each (host buffers).
  * Ops >= 64 are the raw-limb field and point test hooks: 64 words in and 64 words out per lane
- * (the row layout is documented at k_selftest_wide in kernels.hip). */
+ * (the row layout is documented at k_selftest_wide in kernels.hip); ops >= 112 call the scalar
+ * functions of scalar25519.h on rows of the same width (k_selftest_scalar). */
 mv_status mv_selftest(mv_ctx* ctx, int op, const uint32_t* in, uint32_t n, uint32_t* out);
 /* Test entry: the preparation stage of the batch path alone (k_bv_prep, batch.hip), launched by
  * the helper the production path launches it with, for n signatures in host arrays (msg, sig and

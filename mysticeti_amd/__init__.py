@@ -940,8 +940,9 @@ class Engine:
     # ---- diagnostics ----
     def selftest(self, op: int, words: np.ndarray) -> np.ndarray:
         """Ops 0..63 take and return 16-word rows; ops >= SELFTEST_WIDE_OP (raw-limb field and point
-        functions, kernels.hip k_selftest_wide) take and return 64-word rows: `words` must be
-        two-dimensional with that width."""
+        functions, kernels.hip k_selftest_wide; from 112 the scalar functions of scalar25519.h,
+        k_selftest_scalar) take and return 64-word rows: `words` must be two-dimensional with that
+        width."""
         width = 64 if op >= SELFTEST_WIDE_OP else 16
         w = np.asarray(words, dtype=np.uint32)
         if width == 64 and (w.ndim != 2 or w.shape[1] != 64):

@@ -89,6 +89,8 @@ hipError_t launch_block_hash_lane(const uint8_t* buf, const uint64_t* off, const
 hipError_t launch_selftest(int op, const uint32_t* in, uint32_t n, const void* btab, uint32_t* out, hipStream_t s);
 // ops >= SELFTEST_WIDE_OP: raw-limb field and point functions on 64-word rows (kernels.hip k_selftest_wide)
 constexpr int SELFTEST_WIDE_OP = 64;
+// ops >= SELFTEST_SCALAR_OP: the functions of scalar25519.h, same rows (kernels.hip k_selftest_scalar)
+constexpr int SELFTEST_SCALAR_OP = 112;
 hipError_t launch_selftest_wide(int op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
 // batch.hip: random-linear-combination batch verify with exact on-device fallback.
 // The batch is cut into `groups` sub-batches (1..BATCH_MAX_GROUPS, whole 1024-signature

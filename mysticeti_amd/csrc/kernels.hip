@@ -10,6 +10,7 @@
 //   launch_blake2b / launch_block_hash entry points below route between them)
 //   k_selftest       field / scalar primitives for the parity tests
 //   k_selftest_wide  field and point functions on raw limbs (the limb-bound contract's tests)
+//   k_selftest_scalar  the functions of scalar25519.h one by one (the scalar layer's tests)
 //
 // The verify kernel is INT32-VALU bound: HBM traffic is 128 B of
 // input per signature plus the per-lane variable-base tables (2 x 9 cached points,
@@ -740,6 +741,78 @@ __global__ void __launch_bounds__(64) k_selftest_wide(int op, const uint32_t* __
   for (int i = 57; i < 64; i++) o[i] = 0;
 }
 
+// The scalar layer (scalar25519.h) function by function (ops >= 112, 64-word rows as above;
+// tests/test_gpu_scalars.py against tests/scalar_model.py). Each op calls the production function
+// and nothing else; output words not named are zero. Word 36 of a row is the parameter.
+//   112 sc_muladd(a, b, c)   in : words 0..7 a, 8..15 b, 16..23 c          out: words 0..7
+//   113 sc_reduce512(x)      in : words 0..15 x                            out: words 0..7
+//   114 sc_is_canonical(s)   in : words 0..7 s                             out: word 0 (0 / 1)
+//   115 sc_recode16_128(x)   in : words 0..3 x                             out: words 0..3, packed
+//   116 sc_halfsize(k)       in : words 0..7 k                             out: words 0..3 c, word 4 c_neg, words 8..11 d
+//   117 shl_var(x, s)        in : words 0..7 x, parameter s (0..255)       out: words 0..7 shl_var<8>(x, s),
+//                                                                               words 8..11 shl_var<4>(x[0..3], s)
+//   118 len256(x)            in : words 0..7 x                             out: word 0
+//   119 digits               in : words 0..7 sd, 8..15 kd (packed)         out: parameter 0: words 0..31 digit256(sd, i);
+//                                                                               parameter 1: words 0..63 digit16(kd, i)
+//                                                                               (sign-extended to 32 bits)
+// One lane per row, no lane looks at another's.
+__global__ void __launch_bounds__(64) k_selftest_scalar(int op, const uint32_t* __restrict__ in, uint32_t n,
+                                                        uint32_t* __restrict__ out) {
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= n) return;
+  const uint32_t* row = in + 64 * (size_t)gid;
+  uint32_t x[24], y[64];
+#pragma unroll
+  for (int i = 0; i < 24; i++) x[i] = row[i];
+#pragma unroll
+  for (int i = 0; i < 64; i++) y[i] = 0;
+  const uint32_t param = row[36];
+  uint32_t* o = out + 64 * (size_t)gid;
+  switch (op) {
+    case 112: sc_muladd(y, x, x + 8, x + 16); break;
+    case 113: sc_reduce512(y, x); break;
+    case 114: y[0] = sc_is_canonical(x) ? 1u : 0u; break;
+    case 115: sc_recode16_128(y, x); break;
+    case 116: {
+      uint32_t c[4], d[4];
+      bool neg;
+      sc_halfsize(c, neg, d, x);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        y[i] = c[i];
+        y[8 + i] = d[i];
+      }
+      y[4] = neg ? 1u : 0u;
+      break;
+    }
+    case 117: {
+      uint32_t a8[8], r8[8], a4[4], r4w[4];
+#pragma unroll
+      for (int i = 0; i < 8; i++) a8[i] = x[i];
+#pragma unroll
+      for (int i = 0; i < 4; i++) a4[i] = x[i];
+      shl_var<8>(r8, a8, (int)(param & 0xffu));
+      shl_var<4>(r4w, a4, (int)(param & 0xffu));
+#pragma unroll
+      for (int i = 0; i < 8; i++) y[i] = r8[i];
+#pragma unroll
+      for (int i = 0; i < 4; i++) y[8 + i] = r4w[i];
+      break;
+    }
+    case 118: y[0] = (uint32_t)len256(x); break;
+    case 119: {  // the digit index stays a run-time value, as in the callers' loops
+      const int nd = (param & 1u) ? 64 : 32;
+#pragma unroll 1
+      for (int i = 0; i < 64; i++)
+        o[i] = i >= nd ? 0u : (uint32_t)((param & 1u) ? digit16(x + 8, i) : digit256(x, i));
+      return;
+    }
+    default: break;
+  }
+#pragma unroll
+  for (int i = 0; i < 64; i++) o[i] = y[i];
+}
+
 // The number of invalid signatures (status MV_SIG_INVALID: the failures a combined equation
 // can see; s >= l and undecodable points are excluded from it exactly) of n statuses, added to
 // *count (zeroed by the launcher): the single-path feedback of the batch policy (engine.cpp
@@ -820,7 +893,11 @@ hipError_t launch_selftest(int op, const uint32_t* in, uint32_t n, const void* b
 }
 hipError_t launch_selftest_wide(int op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(mv::k_selftest_wide, dim3((n + 63) / 64), dim3(64), 0, s, op, in, n, out);
+  if (op >= SELFTEST_SCALAR_OP) {
+    hipLaunchKernelGGL(mv::k_selftest_scalar, dim3((n + 63) / 64), dim3(64), 0, s, op, in, n, out);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(mv::k_selftest_wide,dim3((n + 63) / 64), dim3(64), 0, s, op, in, n, out);
   return hipGetLastError();
 }
 

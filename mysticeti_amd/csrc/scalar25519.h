@@ -102,23 +102,6 @@ MV_DEV void sc_muladd(uint32_t r[8], const uint32_t a[8], const uint32_t b[8], c
   sc_reduce512(r, t);
 }
 
-// Signed radix-16 recoding of k < 2^253: 64 digits in [-8, 7], packed as
-// 4-bit two's complement, digit i in bits 4(i%8).. of word i/8.
-MV_DEV void sc_recode16(uint32_t out[8], const uint32_t k[8]) {
-  uint32_t carry = 0;
-#pragma unroll
-  for (int w = 0; w < 8; w++) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      uint32_t d = ((k[w] >> (4 * j)) & 15u) + carry;
-      carry = (d + 8) >> 4;  // d in [8, 16] -> digit d - 16, carry 1
-      d = (d - (carry << 4)) & 15u;
-      o |= d << (4 * j);
-    }
-    out[w] = o;
-  }
-}
 // Signed radix-256 recoding of s < 2^253 (s < l; signing reduces its secret scalar
 // mod l first): 32 digits in [-128, 127] packed as int8 bytes, digit i in byte i. The
 // top digit is at most 0x10 + 1, so no carry leaves the last byte.
@@ -149,7 +132,7 @@ MV_DEV void sc_recode16_128(uint32_t out[4], const uint32_t x[4]) {
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       uint32_t d = ((x[w] >> (4 * j)) & 15u) + carry;
-      carry = (d + 8) >> 4;
+      carry = (d + 8) >> 4;  // d in [8, 16] -> digit d - 16, carry 1
       d = (d - (carry << 4)) & 15u;
       o |= d << (4 * j);
     }
