@@ -713,6 +713,73 @@ mv_status mv_seal_blocks(mv_ctx* ctx, uint8_t* buf, const uint64_t* off, const u
                          uint8_t* status /* n, MV_SEAL_* */, uint8_t* msg_digest /* n x 32 or NULL */,
                          uint8_t* block_digest /* n x 32 or NULL */);
 
+/* ---- transaction votes: fast-path certificates per block ----
+ * What BlockHandler::handle_blocks does with the blocks add_blocks returns (core.rs:171-207,
+ * block_handler.rs:146-190): TransactionAggregator::process_block (committee.rs:263-482) over a
+ * store in device memory. State is one cell per (sharing block reference B, statement offset o):
+ * empty, or aggregating with a voter set and a stake sum. Requires mv_set_committee
+ * (MV_E_NO_COMMITTEE) for the stakes and the quorum threshold 2S/3 + 1 (committee.rs:56-57, :79-81).
+ *
+ * A call processes its blocks in order. For block i (author a, reference R):
+ *   1. register (shared_ranges, types.rs:238-254; register, committee.rs:364-384): for every offset
+ *      o of block i holding a Share, an empty cell (R, o) becomes aggregating with voters {a} and
+ *      stake(a) -- the threshold is not tested here; an aggregating cell is left as it is and the
+ *      offset counts as duplicate.
+ *   2. vote, in statement order (process_block :463-479, vote :386-425): Vote(locator, Accept) is
+ *      the range [o, o + 1) of locator.block, VoteRange [start, end) of its block. For every offset
+ *      in ascending order: an empty cell (never registered, certified already, not a Share, past
+ *      the block's statements, a block the store has never seen) counts as unknown; otherwise a
+ *      joins the voters, its stake is added the first time only, and at a stake sum >= the
+ *      threshold the transaction is certified by block i and the cell becomes empty. Share
+ *      statements are skipped.
+ *   3. a sharing block without an aggregating cell is no longer pending (TransactionAggregator::len
+ *      counts the blocks with one).
+ * The call does not verify: callers pass blocks that were MV_BLOCK_OK. A block that does not parse
+ * (what MV_BLOCK_PARSE_ERROR fails) or whose author is outside the committee changes nothing.
+ * Divergences, where the reference has no behaviour to copy: Vote::Reject is unimplemented!()
+ * there (committee.rs:472) and a Vote at offset 2^64 - 1 overflows in one(); here each such
+ * statement is ignored and its block gets a flag bit. A VoteRange with end < start or
+ * end - start >= 2^20 (which verify rejects) counts as empty and is flagged. Blocks with one
+ * reference are taken to be one block: Share offsets of a later block at or past the statement
+ * count of the first block with that reference are ignored and flagged. */
+#define MV_VOTES_OK 0             /* blk_status: processed */
+#define MV_VOTES_PARSE_ERROR 1    /* does not deserialize, or its span leaves the buffer: nothing changed */
+#define MV_VOTES_UNKNOWN_AUTHOR 2 /* author >= the committee size: nothing changed */
+#define MV_VOTES_FLAG_REJECT 1u        /* blk_counts word 3: a Vote::Reject was ignored */
+#define MV_VOTES_FLAG_OFFSET 2u        /* a Vote at offset 2^64 - 1 was ignored */
+#define MV_VOTES_FLAG_RANGE 4u         /* a VoteRange with end < start or end - start >= 2^20 was ignored */
+#define MV_VOTES_FLAG_REF_REUSED 8u    /* Share offsets past the statement count its reference was first seen with */
+#define MV_VOTES_REGISTER_ONLY 1u /* flags: step 1 alone -- handle_proposal for the caller's own blocks
+                                     (block_handler.rs:199-204) */
+/* Makes the store, or grows it, so that `blocks` sharing blocks and `cells` statement offsets fit;
+ * never shrinks, keeps what is stored. Opt-in as mv_dag_reserve: the aggregate calls are
+ * MV_E_INVALID_ARG without it. The voter set is ceil(committee size / 64) words per cell, fixed
+ * here: MV_E_NO_COMMITTEE without a committee; after a committee of another word count
+ * mv_votes_clear, then reserve again. The store grows geometrically inside the aggregate calls;
+ * rows without an aggregating cell are dropped, and their cells reclaimed, before it would grow
+ * and whenever they are half of the cells in use. */
+mv_status mv_votes_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t cells);
+/* Empties the store and zeroes its counters (capacity and voter word count go too: reserve again). */
+mv_status mv_votes_clear(mv_ctx* ctx);
+/* out[0] pending sharing blocks (TransactionAggregator::len), out[1] aggregating cells, out[2] cells
+ * of capacity in use, out[3] transactions certified since create / clear. */
+mv_status mv_votes_stats(mv_ctx* ctx, uint64_t* out /* 4 */);
+/* Processes n blocks buf[off[i], off[i] + len[i]) in order (committee.rs:263-482, see above).
+ * blk_status[i] = MV_VOTES_*; blk_counts holds four words per block: transactions it certified,
+ * unknown offsets, duplicate offsets, MV_VOTES_FLAG_* bits. certified holds 8 words per row: the
+ * sharing block's reference in words 0-5 (authority, round, four digest words), the offset in word
+ * 6, the index in this call of the certifying block in word 7 -- in the order of the reference's
+ * `processed` vectors concatenated: by certifying block, then statement order, then ascending
+ * offset. *n_certified is the total; only the first cap_certified rows are written, and the state
+ * advances in full whatever the cap (as mv_connect_blocks' `connected`). certified may be NULL with
+ * a cap of 0. Runs on the context's first device and takes the context in turn.
+ * MV_E_INVALID_ARG (bad arguments, no store, another voter word count) leaves the store as it was.
+ * After MV_E_HIP or MV_E_ALLOC the store may hold part of the call: mv_votes_clear. */
+mv_status mv_aggregate_votes(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off, const uint64_t* len, uint32_t n,
+                             uint32_t flags, uint8_t* blk_status /* n */, uint64_t* blk_counts /* n x 4 */,
+                             uint64_t* certified /* cap_certified x 8 */, uint64_t cap_certified,
+                             uint64_t* n_certified);
+
 /* ---- device-resident variants (inputs already in HBM of `device`) ----
  * Pointers are device pointers, 16-byte aligned; `stream` is a hipStream_t (NULL = the
  * library's stream for that device). They enqueue work and return without synchronising. */
@@ -842,6 +909,15 @@ mv_status mv_dev_seal_blocks(mv_ctx* ctx, int device, uint8_t* d_buf, uint64_t b
                              const uint64_t* d_len, uint32_t n, const uint8_t* d_seeds, uint32_t n_auth,
                              uint32_t flags, uint8_t* d_status, uint8_t* d_msg_digest, uint8_t* d_block_digest,
                              void* stream);
+/* mv_aggregate_votes (process_block, committee.rs:263-482) on bincode already in HBM of the
+ * context's first device: every array but n_certified is device memory, d_buf 8-byte aligned with 16
+ * readable bytes past buf_bytes, the u64 arrays 8-byte aligned. A block whose span leaves buf_bytes is
+ * MV_VOTES_PARSE_ERROR. Synchronises `stream` (the scan's totals size the event lists and decide
+ * about room). The host-buffer call is a copy in, this call and a copy out. */
+mv_status mv_dev_aggregate_votes(mv_ctx* ctx, int device, const uint8_t* d_buf, uint64_t buf_bytes,
+                                 const uint64_t* d_off, const uint64_t* d_len, uint32_t n, uint32_t flags,
+                                 uint8_t* d_blk_status, uint64_t* d_blk_counts, uint64_t* d_certified,
+                                 uint64_t cap_certified, uint64_t* n_certified, void* stream);
 /* crc32fast::hash of n strings of device buffer d_buf at d_off/d_len (device arrays) -> d_out. Enqueue only. */
 mv_status mv_dev_crc32(mv_ctx* ctx, int device, const uint8_t* d_buf, const uint64_t* d_off, const uint64_t* d_len,
                        uint32_t n, uint32_t* d_out, void* stream);

@@ -81,12 +81,18 @@ EXPORTS = [
     "mv_dag_reserve", "mv_dag_prune", "mv_dag_stats", "mv_decide_leaders", "mv_dev_decide_leaders",
     "mv_commit_leaders", "mv_dev_commit_leaders", "mv_wal_recover", "mv_dev_dag_seed_rows",
     "mv_seal_blocks", "mv_dev_seal_blocks",
+    "mv_votes_reserve", "mv_votes_clear", "mv_votes_stats", "mv_aggregate_votes", "mv_dev_aggregate_votes",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 # per-block outcomes of mv_seal_blocks, and its flag
 SEAL_STATUS = ["OK", "PARSE_ERROR", "UNKNOWN_AUTHOR", "UNLINKED"]
 SEAL_OK, SEAL_PARSE_ERROR, SEAL_UNKNOWN_AUTHOR, SEAL_UNLINKED = range(4)
 SEAL_LINK = 1
+# per-block outcomes of mv_aggregate_votes, the flag bits of a block's fourth count word, the call's flag
+VOTES_STATUS = ["OK", "PARSE_ERROR", "UNKNOWN_AUTHOR"]
+VOTES_OK, VOTES_PARSE_ERROR, VOTES_UNKNOWN_AUTHOR = range(3)
+VOTES_FLAG_REJECT, VOTES_FLAG_OFFSET, VOTES_FLAG_RANGE, VOTES_FLAG_REF_REUSED = 1, 2, 4, 8
+VOTES_REGISTER_ONLY = 1
 WAL_OK, WAL_CRC_MISMATCH, WAL_NONZERO_CRC_LEN0, WAL_BAD_LENGTH = range(4)
 # ... and of the replay loop of BlockStore::open (mv_wal_replay only)
 WAL_UNKNOWN_TAG, WAL_BLOCK_DECODE, WAL_UNKNOWN_AUTHORITY = 4, 5, 6
@@ -174,6 +180,11 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_ed25519_sign.argtypes = [vp, ctypes.c_int, vp, vp, u32, vp, vp, vp]
     lib.mv_seal_blocks.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
     lib.mv_dev_seal_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp]
+    lib.mv_votes_reserve.argtypes = [vp, u64, u64]
+    lib.mv_votes_clear.argtypes = [vp]
+    lib.mv_votes_stats.argtypes = [vp, vp]
+    lib.mv_aggregate_votes.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, u64, vp]
+    lib.mv_dev_aggregate_votes.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, u32, vp, vp, vp, u64, vp, vp]
     lib.mv_selftest.argtypes = [vp, ctypes.c_int, vp, u32, vp]
     lib.mv_selftest_batch_prep.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp]
     lib.mv_selftest_batch_msm.argtypes = [vp, u32, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]
@@ -424,6 +435,59 @@ class Engine:
             d_off.shape[0], vp(d_seeds.data_ptr()), d_seeds.shape[0], SEAL_LINK if link else 0,
             vp(d_status.data_ptr()), vp(d_md.data_ptr()) if d_md is not None else None,
             vp(d_bd.data_ptr()) if d_bd is not None else None, vp(stream_handle or None)), "mv_dev_seal_blocks")
+
+    # ---- transaction votes (committee.rs:263-482) ----
+    def votes_reserve(self, blocks: int, cells: int):
+        """Makes the vote store, or grows it, for `blocks` sharing blocks and `cells` statement offsets
+        (mv_votes_reserve; needs set_committee)."""
+        self._check(self.lib.mv_votes_reserve(self.ctx, int(blocks), int(cells)), "mv_votes_reserve")
+
+    def votes_clear(self):
+        self._check(self.lib.mv_votes_clear(self.ctx), "mv_votes_clear")
+
+    def votes_stats(self) -> "VotesStats":
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.mv_votes_stats(self.ctx, _p(out)), "mv_votes_stats")
+        return VotesStats(*(int(x) for x in out))
+
+    def aggregate_votes(self, blocks: Sequence[bytes], register_only: bool = False, cap_certified: Optional[int] = None):
+        """TransactionAggregator::process_block for each bincode block, in order (mv_aggregate_votes).
+        Returns (status MV_VOTES_*, counts (n, 4) uint64: certified, unknown, duplicate, flag bits,
+        certified rows (k, 8) uint64: reference words 0-5, offset, certifying block, total certified);
+        k = min(total, cap_certified), by default all of them."""
+        n = len(blocks)
+        lens = np.array([len(b) for b in blocks], dtype=np.uint64)
+        offs = np.zeros(n, dtype=np.uint64)
+        if n > 1:
+            offs[1:] = np.cumsum(lens)[:-1]
+        buf = np.frombuffer(b"".join(blocks) + b"\0", dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        counts = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        total = ctypes.c_uint64(0)
+        flags = VOTES_REGISTER_ONLY if register_only else 0
+        cap = 1024 if cap_certified is None else int(cap_certified)
+        rows = np.zeros((max(cap, 1), 8), dtype=np.uint64)
+        self._check(self.lib.mv_aggregate_votes(self.ctx, _p(buf), _p(offs), _p(lens), n, flags, _p(st), _p(counts),
+                                                _p(rows), cap, ctypes.byref(total)), "mv_aggregate_votes")
+        if cap_certified is None and total.value > cap:
+            raise MvError("aggregate_votes: more than 1024 transactions certified; pass cap_certified (the store has "
+                          "advanced)")
+        return st[:n], counts[:n], rows[:min(total.value, cap)].copy(), int(total.value)
+
+    def dev_aggregate_votes(self, device: int, d_buf, buf_bytes: int, d_off, d_len, d_status, d_counts, d_certified=None,
+                            register_only: bool = False, stream_handle: int = 0) -> int:
+        """mv_aggregate_votes on HBM-resident bincode (torch uint8 buffer padded by 16 bytes, int64
+        offsets and lengths, uint8 status, int64 counts (n, 4) and certified rows (cap, 8)).
+        Synchronises the stream; returns the certified total."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64(0)
+        cap = d_certified.shape[0] if d_certified is not None else 0
+        self._check(self.lib.mv_dev_aggregate_votes(
+            self.ctx, device, vp(d_buf.data_ptr()), int(buf_bytes), vp(d_off.data_ptr()), vp(d_len.data_ptr()),
+            d_off.shape[0], VOTES_REGISTER_ONLY if register_only else 0, vp(d_status.data_ptr()),
+            vp(d_counts.data_ptr()), vp(d_certified.data_ptr()) if cap else None, cap, ctypes.byref(total),
+            vp(stream_handle or None)), "mv_dev_aggregate_votes")
+        return int(total.value)
 
     def verify_frames(self, buf):
         """Blocks of received NetworkMessage frames (network.rs:400-447) verified in place:
@@ -1123,6 +1187,18 @@ class IndexStats:
     def __init__(self, have, wanted, capacity, rebuilds, longest_probe):
         self.have, self.wanted, self.capacity = have, wanted, capacity
         self.rebuilds, self.longest_probe = rebuilds, longest_probe
+
+
+class VotesStats:
+    """Result of Engine.votes_stats (mv_votes_stats): pending sharing blocks
+    (TransactionAggregator::len), aggregating cells, cells of capacity in use, transactions
+    certified since create / clear."""
+
+    def __init__(self, pending, aggregating, cells_in_use, certified):
+        self.pending, self.aggregating, self.cells_in_use, self.certified = pending, aggregating, cells_in_use, certified
+
+    def as_tuple(self):
+        return (self.pending, self.aggregating, self.cells_in_use, self.certified)
 
 
 class Accepted:

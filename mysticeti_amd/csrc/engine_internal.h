@@ -1,7 +1,8 @@
 // What the engine's source files share (host only): the per-device state and the context, the
 // error plumbing, the sharding helpers, and the declarations of the functions that cross files
 // (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp,
-// engine_index.cpp, engine_connect.cpp, engine_dag.cpp, engine_decide.cpp, engine_seal.cpp).
+// engine_index.cpp, engine_connect.cpp, engine_dag.cpp, engine_decide.cpp, engine_seal.cpp,
+// engine_votes.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -212,6 +213,20 @@ struct Device {
     DevBuf keys, heads, tab, md, bd, in, ol, st, seeds;
     HostBuf h;
   } seal;
+
+  // mv_aggregate_votes (votes.hip): the store -- its own table, the slot -> row map, the rows and
+  // the cell arena, made by mv_votes_reserve only; growing and reclaiming fill a fresh copy and
+  // swap -- its control words, and a call's per-block, per-event and per-segment scratch, the
+  // insert's records, and the bytes, off | len and results of host-buffer calls
+  struct Votes {
+    bool on = false;
+    DevBuf tab, rowmap, row_key, row_base, row_n, row_agg, cells, ctl;
+    HostBuf h_ctl;
+    uint64_t slots = 0, cap_rows = 0, cap_cells = 0, nrows = 0, ncells = 0;
+    uint32_t voter_words = 0;
+    uint64_t pending = 0, agg = 0, live_cells = 0, certified = 0;  // as of the last call
+    DevBuf blk, evs, seg, item, in, ol, out;
+  } votes;
 
   // the resident online service (k_online) of this device, made on first use
   std::shared_ptr<OnlineSvc> online;

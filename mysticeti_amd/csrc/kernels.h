@@ -727,4 +727,76 @@ constexpr uint32_t SEAL_THROUGHPUT_MIN = 1u << 15;
 hipError_t launch_seal_level(uint8_t* buf, uint64_t buf_bytes, const uint64_t* off, const uint64_t* len, uint32_t lo,
                              uint32_t hi, const uint32_t* keys, const void* btab, const SealTable& t, uint8_t* status,
                              uint8_t* md, uint8_t* bd, hipStream_t s);
+
+// votes.hip: mv_aggregate_votes (TransactionAggregator::process_block, committee.rs:263-482). The
+// store: a table of its own (index_dev.h's layout and hashing, another instance than the block
+// index) from a sharing block's reference to a row, and per row a run of cells in one arena. A
+// cell is cw = 2 + voter words: [0] 0 empty, 1 aggregating, else the mark of the event that
+// certified it in the running call (cleared when its row is written); [1] the stake sum; [2..]
+// the voters. Cells past the arena's cursor are zero.
+struct VoteStore {
+  IndexTable t;
+  uint32_t* rowmap;  // per slot of t: its row
+  uint64_t* row_key;   // 6 words per row
+  uint64_t* row_base;  // the row's first cell
+  uint32_t* row_n;     // its cells: the statement count of the block that made it
+  uint32_t* row_agg;   // of which aggregating
+  uint64_t* cells;
+  uint64_t cap_rows, cap_cells;
+  uint32_t cw;
+};
+// One call: the blocks, the committee, the per-block arrays of the scan (n entries each) and the
+// events (cap_ev entries each). An event is three words: row | kind << 32, start | end << 32 (clipped
+// to the row's cells), voter | block << 32; its id is its position, monotone in (block, statement)
+// with a block's register events ahead of its votes.
+struct VoteCall {
+  const uint8_t* buf;
+  uint64_t buf_bytes;
+  const uint64_t *off, *len;
+  uint32_t n, flags;
+  const uint64_t* stakes;
+  uint32_t n_auth;
+  uint64_t quorum;  // certified at a stake sum >= quorum
+  uint8_t* status;
+  uint64_t *key, *keyoff;  // the own reference's six words; 48 i for a sharing block, else IX_NO_SRC
+  uint32_t *author, *n_st, *nreg, *nev, *bflags;
+  uint64_t *unk, *evbase;  // unknown offsets counted without an event; the block's first event
+  uint8_t* brk;            // the block re-registers a row: a segment starts at it
+  uint64_t* ev;
+  uint32_t *evc, *evx;  // per event: certified; unknown (votes) or duplicate (register)
+  uint64_t cap_ev;
+};
+// the store's control words, behind the IX_CTL_WORDS of its table's insert rounds
+constexpr int VT_CTL_NSHARE = IX_CTL_WORDS, VT_CTL_NEWCELLS = VT_CTL_NSHARE + 1, VT_CTL_NEV = VT_CTL_NSHARE + 2,
+              VT_CTL_NROWS = VT_CTL_NSHARE + 3, VT_CTL_NCELLS = VT_CTL_NSHARE + 4, VT_CTL_ERR = VT_CTL_NSHARE + 5,
+              VT_CTL_NBRK = VT_CTL_NSHARE + 6, VT_CTL_PENDING = VT_CTL_NSHARE + 7, VT_CTL_AGG = VT_CTL_NSHARE + 8,
+              VT_CTL_LIVECELLS = VT_CTL_NSHARE + 9, VT_CTL_NCERT = VT_CTL_NSHARE + 10, VT_CTL_NLIST = VT_CTL_NSHARE + 11,
+              VT_CTL_SEGCERT = VT_CTL_NSHARE + 12, VT_CTL_WORDS = VT_CTL_NSHARE + 16;
+constexpr uint32_t VT_KIND_NONE = 0, VT_KIND_REG = 1, VT_KIND_VOTE = 2;
+// exclusive scan of n u32 counts into u64: out[i], *total; with `running` behind it (launch_index_scan).
+// wg: wg_scan_bytes(n)
+hipError_t launch_votes_scan_u32(const uint32_t* v, uint64_t n, uint64_t* out, uint64_t* total, uint64_t* running,
+                                 void* wg, hipStream_t s);
+// the first walk: the per-block arrays but evbase, brk; ctl[VT_CTL_NSHARE / _NEWCELLS] (zeroed by the caller)
+hipError_t launch_votes_scan(const VoteCall& c, uint64_t* ctl, hipStream_t s);
+// after the insert of the sharing blocks' references (item: its records): the rows of new
+// references, brk, ctl[VT_CTL_NBRK]; then the second walk writes the events
+hipError_t launch_votes_rows(const VoteStore& v, const VoteCall& c, const uint64_t* item, uint64_t* ctl, hipStream_t s);
+hipError_t launch_votes_emit(const VoteStore& v, const VoteCall& c, const uint64_t* item, uint64_t* ctl, hipStream_t s);
+// One segment, events [e0, e1): grouped by row in id order (row_cnt, row_cur: nrows words, row_lb
+// nrows; list, sorted: e1 - e0 words), applied a wave per row, and the certified rows written behind
+// ctl[VT_CTL_NCERT] (which grows), the first cap_cert of the call.
+struct VoteSeg {
+  uint32_t *row_cnt, *row_cur, *list, *sorted;
+  uint64_t *row_lb, *certbase;
+  void* wg;
+};
+hipError_t launch_votes_segment(const VoteStore& v, const VoteCall& c, uint64_t nrows, uint64_t e0, uint64_t e1,
+                                const VoteSeg& g, uint64_t* certified, uint64_t cap_cert, uint64_t* ctl, hipStream_t s);
+// blk_counts (4 words per block) from the events' counts
+hipError_t launch_votes_blockout(const VoteCall& c, uint64_t* blk_counts, hipStream_t s);
+// ctl[VT_CTL_PENDING / _AGG / _LIVECELLS] over the rows
+hipError_t launch_votes_stats(const VoteStore& v, uint64_t nrows, uint64_t* ctl, hipStream_t s);
+// the rows of v with an aggregating cell into q (empty, zeroed); ctl[VT_CTL_NROWS / _NCELLS] = what q holds
+hipError_t launch_votes_move(const VoteStore& v, uint64_t nrows, const VoteStore& q, uint64_t* ctl, hipStream_t s);
 }  // namespace mvk

@@ -72,6 +72,14 @@ pub const MV_SEAL_PARSE_ERROR: u8 = 1;
 pub const MV_SEAL_UNKNOWN_AUTHOR: u8 = 2;
 pub const MV_SEAL_UNLINKED: u8 = 3;
 pub const MV_SEAL_LINK: u32 = 1;
+pub const MV_VOTES_OK: u8 = 0;
+pub const MV_VOTES_PARSE_ERROR: u8 = 1;
+pub const MV_VOTES_UNKNOWN_AUTHOR: u8 = 2;
+pub const MV_VOTES_FLAG_REJECT: u32 = 1;
+pub const MV_VOTES_FLAG_OFFSET: u32 = 2;
+pub const MV_VOTES_FLAG_RANGE: u32 = 4;
+pub const MV_VOTES_FLAG_REF_REUSED: u32 = 8;
+pub const MV_VOTES_REGISTER_ONLY: u32 = 1;
 
 pub const MV_WAL_OK: u8 = 0;
 pub const MV_WAL_CRC_MISMATCH: u8 = 1;
@@ -187,6 +195,16 @@ extern "C" {
                               d_len: *const u64, n: u32, d_seeds: *const u8, n_auth: u32, flags: u32,
                               d_status: *mut u8, d_msg_digest: *mut u8, d_block_digest: *mut u8,
                               stream: *mut c_void) -> i32;
+    pub fn mv_votes_reserve(ctx: *mut mv_ctx, blocks: u64, cells: u64) -> i32;
+    pub fn mv_votes_clear(ctx: *mut mv_ctx) -> i32;
+    pub fn mv_votes_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
+    pub fn mv_aggregate_votes(ctx: *mut mv_ctx, buf: *const u8, off: *const u64, len: *const u64, n: u32,
+                              flags: u32, blk_status: *mut u8, blk_counts: *mut u64, certified: *mut u64,
+                              cap_certified: u64, n_certified: *mut u64) -> i32;
+    pub fn mv_dev_aggregate_votes(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,
+                                  d_off: *const u64, d_len: *const u64, n: u32, flags: u32,
+                                  d_blk_status: *mut u8, d_blk_counts: *mut u64, d_certified: *mut u64,
+                                  cap_certified: u64, n_certified: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_dev_verify_frames(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64,
                                 d_soff: *const u64, d_slen: *const u64, ns: u32, d_consumed: *mut u64,
                                 d_drop_msg: *mut u32, d_msgs: *mut u32, cap_msgs: u64, n_msgs: *mut u64,
