@@ -61,6 +61,8 @@
  *                          every add_blocks
  *   mv_commit_leaders      try_commit itself: the direct rule, try_indirect_decide (:294-318) over
  *                          BlockStore::linked_to_round (block_store.rs:306-327), and the decided prefix
+ *   mv_linearize           Linearizer::handle_commit (consensus/linearizer.rs:125-166): each committed leader's
+ *                          sub-DAG in the reference's own order, with the committed marks and last_height
  *   mv_seal_blocks         StatementBlock::new_with_signer (types.rs:155-218) on blocks that are bincode
  *                          already: Signer::sign_block (crypto.rs:199-223) over the digest of the signed
  *                          pre-image (crypto.rs:85-128) and BlockDigest::new (crypto.rs:38-61), written
@@ -565,7 +567,8 @@ mv_status mv_dag_stats(mv_ctx* ctx, uint64_t* out /* 4 */);
  * equivocate in the voting round, a quorum of blame can stand beside a leader block with enough
  * support; blame is tested first, here as in the reference, so fewer records can uncover that COMMIT.)
  * What stays with the caller: try_indirect_decide (:294-318), the longest-decided-prefix rule and
- * the genesis filter of UniversalCommitter::try_commit (mv_commit_leaders runs these), and the linearizer.
+ * the genesis filter of UniversalCommitter::try_commit (mv_commit_leaders runs these); the linearizer is
+ * mv_linearize.
  * Requires mv_set_committee (MV_E_NO_COMMITTEE) and mv_dag_reserve (MV_E_INVALID_ARG without the
  * store). n = 0 does nothing. Results do not depend on MV_INDEX_TAG_BITS, on the order blocks were
  * delivered in, or on launch geometry. */
@@ -615,11 +618,64 @@ mv_status mv_decide_leaders(mv_ctx* ctx, const uint64_t* leaders /* n x 2: autho
  * out row i: as mv_decide_leaders (words 0-5 the committed reference, 6 the status, 7 the leader
  * blocks found). info row i: word 0 the kind, 1 the anchor's row (all ones without one), 2 the flags,
  * 3 the records in reach[r + 2].
- * What stays with the caller: leader election, last_decided, and the linearizer.
+ * What stays with the caller: leader election and last_decided (the linearizer is mv_linearize).
  * Requirements and refusals as mv_decide_leaders; n = 0 sets *n_sequence = 0. The call leaves no
  * state behind: a later mv_decide_leaders or mv_commit_leaders reads the store alone. */
 mv_status mv_commit_leaders(mv_ctx* ctx, const uint64_t* leaders /* n x 2, in sequence order */, uint32_t n,
                             uint64_t* out /* n x 8 */, uint64_t* info /* n x 4 */, uint64_t* n_sequence);
+
+#define MV_LINEAR_OK 0
+#define MV_LINEAR_INCOMPLETE 1 /* the leader, or a block of its sub-DAG above round 0, has no record */
+#define MV_LINEAR_COMMITTED 2  /* the leader is already marked (the reference asserts) */
+#define MV_LINEAR_OVERFLOW 3   /* a path deeper than MV_LINEAR_MAX_DEPTH, an include number above
+                                  MV_LINEAR_MAX_INCLUDE, or the sub-DAG does not fit in cap */
+#define MV_LINEAR_STOPPED 4    /* a row behind the first row that is not OK */
+#define MV_LINEAR_MAX_DEPTH 16
+#define MV_LINEAR_MAX_INCLUDE 65534
+#define MV_LINEAR_MAX_LEADERS 65535
+/* Linearizer::handle_commit (consensus/linearizer.rs:125-166): every committed leader block becomes
+ * its CommittedSubDag, the blocks in the reference's own order. State per context, beside the DAG
+ * store: a committed mark per reference (Linearizer::committed) and last_height.
+ * The reference marks a block when it is pushed and expands it when it is popped, so a block belongs
+ * to the includer that is popped first, and an includer's round is higher than the block's. The pop
+ * order is therefore the preorder of a tree that is built round by round, top down. For leader block
+ * L of round R that is not marked:
+ *   1. path(L) = (), L is marked, the sub-DAG is {L}.
+ *   2. For q = R - 1 down to 0: every unmarked reference b whose key round is q and that is include
+ *      number j (from 0 in include order, duplicates counted) of a member x. Of all such (x, j) the
+ *      least pair (path(x), j) -- paths compare component by component, a prefix before its
+ *      extensions -- gives path(b) = path(x) ++ (0xffff - j); b is marked and joins.
+ *   3. The members sorted by (round, path), both ascending: collect_sub_dag and the stable
+ *      sort_by_key(round). last_height += 1.
+ * Leaders are taken in the order given; each sees the marks of those before it.
+ * Where this store differs from the reference's (which has every block of a stored block's sub-DAG):
+ * an unmarked include without a record whose round is 0 (seeded genesis) is a leaf, put out and
+ * marked; one whose round is above 0 makes the leader MV_LINEAR_INCOMPLETE, as a leader without a
+ * record is; a marked reference is passed over with or without a record.
+ * A path holds MV_LINEAR_MAX_DEPTH components: a member whose least pair has an x that deep, or a
+ * j above MV_LINEAR_MAX_INCLUDE, makes the leader MV_LINEAR_OVERFLOW and does not join. A leader that
+ * meets more than one of these reports the highest status number.
+ * blocks: the sub-DAGs one behind the other, six words per block; *n_rows the rows written.
+ * sub row i: word 0 the status, 1 the first row, 2 the count, 3 the height. A leader whose rows do
+ * not fit in cap is MV_LINEAR_OVERFLOW. Rows behind the first row that is not OK are MV_LINEAR_STOPPED;
+ * a row that is not OK has first row = *n_rows, count 0, height 0.
+ * State changes only for the OK prefix: a row that is not OK leaves marks and height as its OK
+ * predecessors left them. The caller then linearizes that leader itself and reports it with
+ * mv_linearize_mark.
+ * Requires mv_dag_reserve (MV_E_INVALID_ARG without it); more than MV_LINEAR_MAX_LEADERS leaders:
+ * MV_E_INVALID_ARG. n = 0 does nothing. mv_index_clear empties marks and height; index rebuilds,
+ * store growth and mv_dag_prune keep them (marks are held per slot of the index). */
+mv_status mv_linearize(mv_ctx* ctx, const uint64_t* leaders /* n x 6 references, sequence order */, uint32_t n,
+                       uint64_t* blocks /* cap x 6 */, uint64_t cap, uint64_t* sub /* n x 4 */, uint64_t* n_rows);
+/* Linearizer::recover_state (linearizer.rs:108-121), and the report after a row that was not OK:
+ * marks the references and sets last_height = max(last_height, height). Every reference goes
+ * through mv_index_insert_stored's insert: one without an index entry gets one, and an entry that
+ * is MV_REF_WANTED or MV_REF_HAVE rises to MV_REF_STORED -- a committed block is a stored block
+ * (the reference commits only what its block store holds), so a later connect call counts it as
+ * an include that is there, and mv_index_wanted no longer lists it. */
+mv_status mv_linearize_mark(mv_ctx* ctx, const uint64_t* refs /* n x 6 */, uint64_t n, uint64_t height);
+/* out[0] = the marked references, out[1] = last_height */
+mv_status mv_linearize_stats(mv_ctx* ctx, uint64_t* out /* 2 */);
 
 /* ---- seeding the DAG store from a replayed WAL ----
  * mv_wal_replay, then one seed call over all its rows while the image is still in device memory:
@@ -896,6 +952,10 @@ mv_status mv_dev_decide_leaders(mv_ctx* ctx, int device, const uint64_t* d_leade
  * *n_sequence on the host. The rows are read back to be checked and grouped; `stream` is synchronised. */
 mv_status mv_dev_commit_leaders(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_out,
                                 uint64_t* d_info, uint64_t* n_sequence, void* stream);
+/* mv_linearize with the leaders, the blocks and the sub rows in HBM of the context's first device;
+ * *n_rows on the host. `stream` is synchronised (the edge counts size the levels' launches). */
+mv_status mv_dev_linearize(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_blocks,
+                           uint64_t cap, uint64_t* d_sub, uint64_t* n_rows, void* stream);
 /* mv_seal_blocks on blocks already in HBM (new_with_signer as there: types.rs:155-218,
  * crypto.rs:38-61, 199-223): the image is patched in place. Every array is device memory; d_buf is
  * 8-byte aligned with 16 readable bytes past buf_bytes, d_seeds 4-byte and the digest arrays (n x 32,

@@ -39,6 +39,9 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.commit_leaders (and dev_commit_leaders)
                            UniversalCommitter::try_commit over them (universal_committer.rs:30-90): the direct
                            rule, try_indirect_decide (base_committer.rs:294-318) and the decided prefix
+  Engine.linearize (and dev_linearize, linearize_mark, linearize_stats)
+                           Linearizer::handle_commit (linearizer.rs:125-166): the committed leaders' sub-DAGs in
+                           the reference's order, with the committed marks and last_height kept in the engine
   Engine.dev_accept_blocks, Engine.dev_connect_blocks, Engine.dev_index_insert
                            the same on buffers already in HBM (a replay's rows go in at a stride)
   frame_messages           the frame and message walk alone, on the host, for one stream
@@ -80,6 +83,7 @@ EXPORTS = [
     "mv_index_insert_stored", "mv_connect_blocks", "mv_dev_connect_blocks", "mv_pending_reserve", "mv_pending_stats",
     "mv_dag_reserve", "mv_dag_prune", "mv_dag_stats", "mv_decide_leaders", "mv_dev_decide_leaders",
     "mv_commit_leaders", "mv_dev_commit_leaders", "mv_wal_recover", "mv_dev_dag_seed_rows",
+    "mv_linearize", "mv_dev_linearize", "mv_linearize_mark", "mv_linearize_stats",
     "mv_seal_blocks", "mv_dev_seal_blocks",
     "mv_votes_reserve", "mv_votes_clear", "mv_votes_stats", "mv_aggregate_votes", "mv_dev_aggregate_votes",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
@@ -117,6 +121,10 @@ DECIDE_MAX_LEADER_BLOCKS = 8
 COMMIT_KIND_NONE, COMMIT_KIND_DIRECT, COMMIT_KIND_INDIRECT = range(3)
 COMMIT_INCOMPLETE, COMMIT_BLOCKED = 1, 2
 COMMIT_NO_ANCHOR = 0xFFFFFFFFFFFFFFFF
+# mv_linearize: word 0 of a sub row, and the limits of a path
+LINEAR_STATUS = ["OK", "INCOMPLETE", "COMMITTED", "OVERFLOW", "STOPPED"]
+LINEAR_OK, LINEAR_INCOMPLETE, LINEAR_COMMITTED, LINEAR_OVERFLOW, LINEAR_STOPPED = range(5)
+LINEAR_MAX_DEPTH, LINEAR_MAX_INCLUDE, LINEAR_MAX_LEADERS = 16, 0xFFFE, 0xFFFF
 WAL_MAP_BITS, WAL_MAP_BITS_TEST = 24, 16  # wal.rs:95-103
 # batch path stages, the block pipeline's, the WAL replay's (mv_stage_times order, MV_NSTAGES)
 STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "hash", "verify", "verdict", "wal_walk",
@@ -230,6 +238,10 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_decide_leaders.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, vp]
     lib.mv_commit_leaders.argtypes = [vp, vp, u32, vp, vp, vp]
     lib.mv_dev_commit_leaders.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, vp, vp]
+    lib.mv_linearize.argtypes = [vp, vp, u32, vp, u64, vp, vp]
+    lib.mv_dev_linearize.argtypes = [vp, ctypes.c_int, vp, u32, vp, u64, vp, vp, vp]
+    lib.mv_linearize_mark.argtypes = [vp, vp, u64, u64]
+    lib.mv_linearize_stats.argtypes = [vp, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     lib.mv_host_free.argtypes = [vp, vp]
     lib.mv_host_free.restype = None
@@ -993,6 +1005,38 @@ class Engine:
                                                    vp(stream_handle or None)), "mv_dev_commit_leaders")
         return int(n_seq.value)
 
+    def linearize(self, leaders, cap: int = 1 << 16) -> "Linearized":
+        """The sub-DAGs of the committed leader blocks `leaders` ((n, 6) references in sequence order), in
+        the reference's order (mv_linearize); at most `cap` blocks in all."""
+        rows = ref_words(leaders)
+        n, cap = rows.shape[0], int(cap)
+        blocks, sub = np.zeros((max(cap, 1), 6), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        n_rows = ctypes.c_uint64(0)
+        self._check(self.lib.mv_linearize(self.ctx, _p(rows) if n else None, n, _p(blocks) if cap else None, cap,
+                                          _p(sub) if n else None, ctypes.byref(n_rows)), "mv_linearize")
+        return Linearized(blocks[:int(n_rows.value)], sub, int(n_rows.value))
+
+    def dev_linearize(self, device: int, d_leaders, d_blocks, d_sub, stream_handle: int = 0) -> int:
+        """mv_dev_linearize on torch device tensors: d_leaders (n, 6), d_blocks (cap, 6), d_sub (n, 4), all
+        int64. Returns the rows written."""
+        vp = ctypes.c_void_p
+        n_rows = ctypes.c_uint64(0)
+        self._check(self.lib.mv_dev_linearize(self.ctx, device, vp(d_leaders.data_ptr()), d_leaders.shape[0],
+                                              vp(d_blocks.data_ptr()), d_blocks.shape[0], vp(d_sub.data_ptr()),
+                                              ctypes.byref(n_rows), vp(stream_handle or None)), "mv_dev_linearize")
+        return int(n_rows.value)
+
+    def linearize_mark(self, refs, height: int = 0):
+        """Marks the references (n, 6) as committed and raises last_height to `height` (mv_linearize_mark)."""
+        rows = ref_words(refs)
+        n = rows.shape[0]
+        self._check(self.lib.mv_linearize_mark(self.ctx, _p(rows) if n else None, n, int(height)), "mv_linearize_mark")
+
+    def linearize_stats(self) -> "LinearStats":
+        out = np.zeros(2, dtype=np.uint64)
+        self._check(self.lib.mv_linearize_stats(self.ctx, _p(out)), "mv_linearize_stats")
+        return LinearStats(int(out[0]), int(out[1]))
+
     def dev_index_insert(self, device: int, d_words, stride_words: int, n: int, state: int = REF_HAVE,
                          stream_handle: int = 0, word_offset: int = 0):
         """mv_dev_index_insert: reference i is the six int64 words of torch device tensor d_words at
@@ -1235,6 +1279,27 @@ class DagStats:
 
     def __init__(self, records, includes, lowest_round, highest_round):
         self.records, self.includes, self.lowest_round, self.highest_round = records, includes, lowest_round, highest_round
+
+
+class Linearized:
+    """Result of Engine.linearize (mv_linearize): blocks (n_rows, 6) uint64, the sub-DAGs one behind the
+    other; sub (n, 4) uint64 -- LINEAR_* status, first row, count, height; n_rows."""
+
+    def __init__(self, blocks, sub, n_rows):
+        self.blocks, self.sub, self.n_rows = blocks, sub, n_rows
+        self.status = sub[:, 0].astype(np.int64)
+
+    def sub_dag(self, i):
+        """The blocks of leader i, as tuples of six words."""
+        first, count = int(self.sub[i, 1]), int(self.sub[i, 2])
+        return [tuple(int(w) for w in row) for row in self.blocks[first:first + count]]
+
+
+class LinearStats:
+    """Result of Engine.linearize_stats (mv_linearize_stats): the marked references and last_height."""
+
+    def __init__(self, marked, last_height):
+        self.marked, self.last_height = marked, last_height
 
 
 class Seeded:

@@ -158,6 +158,8 @@ mv_status mv_dag_reserve(mv_ctx* ctx, uint64_t blocks, uint64_t includes) {
   if (!dg.on && ix.slots) {  // the map of the table in force (a later table brings its own)
     HIPCHK(ctx, dg.map.ensure(4 * (size_t)ix.slots));
     dg.map_slots = ix.slots;
+    HIPCHK(ctx, dg.lmark.ensure(4 * (size_t)ix.slots));  // the linearizer's marks, as long as the map
+    HIPCHK(ctx, hipMemsetAsync(dg.lmark.p, 0, 4 * (size_t)ix.slots, s));
     HIPCHK(ctx, mvk::launch_dag_map(dag_view(dg), 0, ix.ctl.as<uint64_t>(), s));
     HIPCHK(ctx, hipStreamSynchronize(s));
   }

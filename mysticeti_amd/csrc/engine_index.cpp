@@ -74,9 +74,20 @@ mv_status index_resize(mv_ctx* ctx, Device& dev, uint64_t slots, hipStream_t s) 
     d.map = fresh_map.as<uint32_t>(), d.n_slots = slots;
     HIPCHK(ctx, mvk::launch_dag_map(d, ix.dag.nb, ix.ctl.as<uint64_t>(), s));
   }
+  // ... and so are the linearizer's committed marks, which follow their keys into the new table
+  DevBuf fresh_mark;
+  if (ix.dag.on) {
+    const mvk::IndexTable nt{fresh.as<unsigned long long>(), slots - 1, ctx->index_secret[0], ctx->index_secret[1], bits};
+    st = linear_marks_for(ctx, dev, old_slots, nt, slots, fresh_mark, s);
+    if (st != MV_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+  }
   HIPCHK(ctx, hipStreamSynchronize(s));  // the old table is read until here; `fresh` frees it below
   if (ix.dag.on) {
     std::swap(ix.dag.map, fresh_map);
+    std::swap(ix.dag.lmark, fresh_mark);
     ix.dag.map_slots = slots;
   }
   std::swap(ix.tab, fresh);
@@ -364,9 +375,12 @@ mv_status mv_index_clear(mv_ctx* ctx) {
   Index& ix = dev->index;
   ix.pend.nb = ix.pend.ni = ix.pend.levels = 0;  // the store's records are slots of the table
   ix.dag.nb = ix.dag.ni = 0;                     // ... and so are the DAG store's
+  ix.dag.lin_marked = ix.dag.lin_height = 0;     // ... and the linearizer's marks
   if (!ix.slots) return MV_OK;
-  if (ix.dag.on && ix.dag.map_slots)
+  if (ix.dag.on && ix.dag.map_slots) {
     HIPCHK(ctx, hipMemsetAsync(ix.dag.map.p, 0xff, 4 * (size_t)ix.dag.map_slots, dev->stream));
+    HIPCHK(ctx, hipMemsetAsync(ix.dag.lmark.p, 0, 4 * (size_t)ix.dag.map_slots, dev->stream));
+  }
   HIPCHK(ctx, hipMemsetAsync(ix.tab.p, 0, kSlotBytes * ix.slots, dev->stream));
   HIPCHK(ctx, hipMemsetAsync(ix.ctl.p, 0, 8 * mvk::IX_CTL_WORDS, dev->stream));
   HIPCHK(ctx, hipStreamSynchronize(dev->stream));

@@ -1,8 +1,8 @@
 // What the engine's source files share (host only): the per-device state and the context, the
 // error plumbing, the sharding helpers, and the declarations of the functions that cross files
 // (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp,
-// engine_index.cpp, engine_connect.cpp, engine_dag.cpp, engine_decide.cpp, engine_seal.cpp,
-// engine_votes.cpp).
+// engine_index.cpp, engine_connect.cpp, engine_dag.cpp, engine_decide.cpp, engine_linearize.cpp,
+// engine_seal.cpp, engine_votes.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -204,6 +204,12 @@ struct Device {
       // rows, per-row state, per-record lists, supports and results; a commit call's certificate
       // masks, per-row chain state, per-job marks and the records of its round span
       DevBuf src, newbase, lead, state, lists, sup, res, cmask, cm, marks, span;
+      // mv_linearize: the committed mark per slot of the table (as long as map, remade with it and
+      // carried over), the marked references and last_height; a call's control words, leaders, per-slot
+      // keys, per-record and per-node arrays, buckets, edges and results
+      DevBuf lmark;
+      uint64_t lin_marked = 0, lin_height = 0;
+      DevBuf lctl, llead, lbest, lnode, lbk, ledge, lres;
     } dag;
   } index;
 
@@ -521,6 +527,12 @@ mv_status dag_room(mv_ctx* ctx, Device& dev, uint64_t more_b, uint64_t more_i, h
 mv_status dag_seed_run(mv_ctx* ctx, Device& dev, const uint8_t* d_img, uint64_t size, const uint64_t* d_rows,
                        const uint8_t* d_status, uint64_t n, uint64_t floor_round, bool can_grow, hipStream_t s,
                        uint64_t* seeded);
+
+// engine_linearize.cpp: the committed marks follow the table -- a zeroed array for `slots` slots that, with
+// marks set, takes over those of the table in force (old_slots of them) under the new table nt. The
+// caller swaps it into dg.lmark once s has been synchronised.
+mv_status linear_marks_for(mv_ctx* ctx, Device& dev, uint64_t old_slots, const mvk::IndexTable& nt, uint64_t slots,
+                           DevBuf& fresh, hipStream_t s);
 
 // engine_online.cpp
 bool online_eligible(mv_ctx* ctx, uint32_t n, uint64_t bytes, uint64_t longest);

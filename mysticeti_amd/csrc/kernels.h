@@ -697,6 +697,70 @@ hipError_t launch_commit_resolve(const IndexTable& t, const DagStore& d, uint64_
 // ctl[IX_CTL_CM_NSEQ] = the rows of the longest prefix of COMMIT / SKIP rows among those of round > 0
 hipError_t launch_commit_prefix(const DecideIn& in, const uint64_t* out, uint64_t* ctl, hipStream_t s);
 
+// One linearize call (mv_linearize; kernels: linearize.hip): the leaders' sub-DAGs in one top-down
+// sweep over the stored edges. mark is the context's committed mark per slot of the table (kept
+// between calls, carried over by a rebuild); everything else is made per call.
+constexpr int LN_KEY_WORDS = 5;    // a pick key: cidx | the includer's 16 path components | the include number
+constexpr int LN_PATH_WORDS = 4;   // 16 components of 16 bits, the first in the top bits of word 0
+constexpr uint32_t LN_MAX_DEPTH = 16, LN_MAX_J = 0xffff, LN_MAX_LEADERS = 0xffff;
+// LN_CTL_LO: the lowest rec_low over the nodes so far -- no level below it has work (all ones before the first node)
+constexpr int LN_CTL_NNODES = 0, LN_CTL_NOK = 1, LN_CTL_NROWS = 2, LN_CTL_NEWMARK = 3, LN_CTL_LO = 4, LN_CTL_WORDS = 8;
+struct LinEdge {
+  uint32_t rec, j;  // the including record, the include's number in its list
+  uint64_t slot;    // the included reference
+};
+struct LinState {
+  uint32_t* mark;         // per slot: committed (the counterpart of Linearizer::committed)
+  uint64_t* best;         // per slot x LN_KEY_WORDS: the least pick key so far, word by word (all ones: none)
+  uint32_t* node_of_rec;  // per record: its node in this call, DG_NONE without one
+  uint64_t* rec_low;      // per record: the lowest round of an include that was not marked before the call (all ones: none)
+  // per node, in the order the take steps made them (the nodes of one level are consecutive)
+  uint64_t* n_slot;
+  uint64_t* n_round;
+  uint64_t* n_path;       // x LN_PATH_WORDS
+  uint32_t* n_cidx;       // the sequence number of its leader
+  uint32_t* n_depth;
+  uint32_t* n_t;          // its number among its leader's nodes, in take order
+  uint32_t* n_lvl;        // the level that made it
+  uint64_t node_cap;
+  // per leader
+  const uint64_t* leaders;  // n x 6
+  uint64_t* root_slot;      // DG_NO_SLOT: no entry, no record, or marked
+  uint32_t* fail;           // 0, or the highest MV_LINEAR_* its sweep met
+  uint32_t* total;          // its nodes
+  uint64_t* first;          // its first output row
+  uint64_t n;
+  // per level of the call, and one behind: the nodes made before it
+  uint64_t* lvl_start;
+  uint64_t n_levels;
+  // the edges, bucketed by the included reference's round: bucket 0 holds the rounds below lo
+  uint32_t* bk_count;       // per bucket (count pass), then the fill pass's cursors
+  const uint64_t* bk_off;   // nbk + 1: where each bucket starts
+  LinEdge* edges;
+  uint64_t nbk, lo, hi, n_edges;  // buckets, the store's lowest record round, the highest leader round
+  uint64_t* lctl;           // LN_CTL_*
+};
+// the leaders' slots (a probe of the table), their refusals, their root keys into best
+hipError_t launch_linear_roots(const IndexTable& t, const DagStore& d, uint64_t nb, const LinState& ls, uint64_t* ctl,
+                               hipStream_t s);
+// fill == false: bk_count[bucket] += the includes of every record of round <= hi; true: the edges
+hipError_t launch_linear_edges(const IndexTable& t, const DagStore& d, uint64_t nb, const LinState& ls, bool fill,
+                               uint64_t* ctl, hipStream_t s);
+// one level: the edges [e0, e0 + ne) end in it; `round` is its round (roots of that round join), all
+// ones for bucket 0. LN_KEY_WORDS pick launches, then the take step.
+hipError_t launch_linear_level(const IndexTable& t, const DagStore& d, uint64_t nb, const LinState& ls, uint64_t level,
+                               uint64_t round, uint64_t e0, uint64_t ne, uint64_t* ctl, hipStream_t s);
+// statuses, first rows, counts and heights (sub: n x 4), the prefix rule; then the OK prefix's nodes
+// into blocks (cap x 6) in (leader, round, path) order and into the marks
+hipError_t launch_linear_output(const IndexTable& t, const LinState& ls, uint64_t height0, uint64_t cap, uint64_t* sub,
+                                uint64_t* blocks, uint64_t* ctl, hipStream_t s);
+// mark[slot of item i] = 1 for the n records of an insert; lctl[LN_CTL_NEWMARK] += those newly set
+hipError_t launch_linear_mark(const uint64_t* item, uint64_t n, uint32_t* mark, uint64_t n_slots, uint64_t* lctl,
+                              uint64_t* ctl, hipStream_t s);
+// after launch_index_rebuild: the marks of the old table's slots onto the same keys' slots in t
+hipError_t launch_linear_carry(const uint64_t* old_slots, uint64_t n_old, const uint32_t* old_mark, const IndexTable& t,
+                               uint32_t* mark, uint64_t* ctl, hipStream_t s);
+
 // seal.hip: mv_seal_blocks (StatementBlock::new_with_signer on bincode blocks with placeholder
 // digest and signature fields). keys: 24 words per authority (a mod l, prefix, public key).
 hipError_t launch_seal_keys(const uint8_t* seeds, uint32_t n_auth, const void* btab, uint32_t* keys, hipStream_t s);

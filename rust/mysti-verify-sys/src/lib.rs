@@ -48,6 +48,14 @@ pub const MV_COMMIT_KIND_DIRECT: u64 = 1;
 pub const MV_COMMIT_KIND_INDIRECT: u64 = 2;
 pub const MV_COMMIT_INCOMPLETE: u64 = 1;
 pub const MV_COMMIT_BLOCKED: u64 = 2;
+pub const MV_LINEAR_OK: u64 = 0;
+pub const MV_LINEAR_INCOMPLETE: u64 = 1;
+pub const MV_LINEAR_COMMITTED: u64 = 2;
+pub const MV_LINEAR_OVERFLOW: u64 = 3;
+pub const MV_LINEAR_STOPPED: u64 = 4;
+pub const MV_LINEAR_MAX_DEPTH: u64 = 16;
+pub const MV_LINEAR_MAX_INCLUDE: u64 = 65534;
+pub const MV_LINEAR_MAX_LEADERS: u64 = 65535;
 
 pub const MV_SIG_OK: u8 = 0;
 pub const MV_SIG_INVALID: u8 = 1;
@@ -183,6 +191,12 @@ extern "C" {
                              n_sequence: *mut u64) -> i32;
     pub fn mv_dev_commit_leaders(ctx: *mut mv_ctx, device: i32, d_leaders: *const u64, n: u32, d_out: *mut u64,
                                  d_info: *mut u64, n_sequence: *mut u64, stream: *mut c_void) -> i32;
+    pub fn mv_linearize(ctx: *mut mv_ctx, leaders: *const u64, n: u32, blocks: *mut u64, cap: u64, sub: *mut u64,
+                        n_rows: *mut u64) -> i32;
+    pub fn mv_dev_linearize(ctx: *mut mv_ctx, device: i32, d_leaders: *const u64, n: u32, d_blocks: *mut u64, cap: u64,
+                            d_sub: *mut u64, n_rows: *mut u64, stream: *mut c_void) -> i32;
+    pub fn mv_linearize_mark(ctx: *mut mv_ctx, refs: *const u64, n: u64, height: u64) -> i32;
+    pub fn mv_linearize_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
     pub fn mv_dev_index_insert(ctx: *mut mv_ctx, device: i32, d_words: *const u64, stride_words: u64, n: u64,
                                state: u32, stream: *mut c_void) -> i32;
     pub fn mv_dev_dag_seed_rows(ctx: *mut mv_ctx, device: i32, d_wal: *const u8, size: u64, d_blk_rows: *const u64,

@@ -333,8 +333,9 @@ impl GpuVerifier {
 
     /// BaseCommitter::try_direct_decide (consensus/base_committer.rs:323-357) for every elected
     /// leader (authority, round) of `leaders`, on the GPU (mv_decide_leaders). The caller elects
-    /// the leaders, and runs try_indirect_decide, the longest-decided-prefix rule and the
-    /// linearizer on the rows; an MV_LEADER_OVERFLOW row it decides itself.
+    /// the leaders, and runs try_indirect_decide and the longest-decided-prefix rule on the rows
+    /// (`commit_leaders` does both; the linearizer is `linearize`); an MV_LEADER_OVERFLOW row it
+    /// decides itself.
     pub fn decide_leaders(&self, leaders: &[(u64, u64)]) -> eyre::Result<Decided> {
         let n = leaders.len();
         let flat: Vec<u64> = leaders.iter().flat_map(|&(a, r)| [a, r]).collect();
@@ -350,9 +351,9 @@ impl GpuVerifier {
     /// (mv_commit_leaders): the direct rule, try_indirect_decide and the decided prefix for the
     /// elected leaders (authority, round) of `leaders`, which stand in the order try_commit's deque
     /// ends in: ascending round, within a round in committer order, after last_decided. The caller
-    /// elects the leaders, keeps last_decided and runs the linearizer on the first `n_sequence`
-    /// rows of round > 0; a row with MV_COMMIT_INCOMPLETE it decides itself once the store holds
-    /// the missing blocks.
+    /// elects the leaders, keeps last_decided and hands the committed references of the first
+    /// `n_sequence` rows of round > 0 to `linearize`; a row with MV_COMMIT_INCOMPLETE it decides
+    /// itself once the store holds the missing blocks.
     pub fn commit_leaders(&self, leaders: &[(u64, u64)]) -> eyre::Result<Committed> {
         let n = leaders.len();
         let flat: Vec<u64> = leaders.iter().flat_map(|&(a, r)| [a, r]).collect();
@@ -364,6 +365,48 @@ impl GpuVerifier {
         ensure!(rc == sys::MV_OK, "mv_commit_leaders: {}", self.last_error());
         Ok(c)
     }
+
+    /// Linearizer::handle_commit (consensus/linearizer.rs:125-166) on the GPU (mv_linearize): the
+    /// sub-DAG of every committed leader block of `leaders` (six words per reference, in sequence
+    /// order), in the reference's order; at most `cap` blocks in all. The committed marks and
+    /// last_height live in the engine. A row that is not MV_LINEAR_OK the caller linearizes itself
+    /// and reports with `linearize_mark`.
+    pub fn linearize(&self, leaders: &[[u64; 6]], cap: usize) -> eyre::Result<Linearized> {
+        let n = leaders.len();
+        let flat: Vec<u64> = leaders.iter().flatten().copied().collect();
+        let mut l = Linearized { blocks: vec![0u64; 6 * cap.max(1)], sub: vec![0u64; 4 * n], n_rows: 0 };
+        let rc = unsafe {
+            sys::mv_linearize(self.ctx, flat.as_ptr(), n as u32, l.blocks.as_mut_ptr(), cap as u64, l.sub.as_mut_ptr(),
+                              &mut l.n_rows)
+        };
+        ensure!(rc == sys::MV_OK, "mv_linearize: {}", self.last_error());
+        l.blocks.truncate(6 * l.n_rows as usize);
+        Ok(l)
+    }
+
+    /// Linearizer::recover_state (linearizer.rs:108-121): marks `refs` as committed and raises
+    /// last_height to `height` (mv_linearize_mark).
+    pub fn linearize_mark(&self, refs: &[[u64; 6]], height: u64) -> eyre::Result<()> {
+        let flat: Vec<u64> = refs.iter().flatten().copied().collect();
+        let rc = unsafe { sys::mv_linearize_mark(self.ctx, flat.as_ptr(), refs.len() as u64, height) };
+        ensure!(rc == sys::MV_OK, "mv_linearize_mark: {}", self.last_error());
+        Ok(())
+    }
+
+    /// (marked references, last_height) (mv_linearize_stats)
+    pub fn linearize_stats(&self) -> eyre::Result<(u64, u64)> {
+        let mut out = [0u64; 2];
+        let rc = unsafe { sys::mv_linearize_stats(self.ctx, out.as_mut_ptr()) };
+        ensure!(rc == sys::MV_OK, "mv_linearize_stats: {}", self.last_error());
+        Ok((out[0], out[1]))
+    }
+}
+
+/// Result of `GpuVerifier::linearize` (layout: include/mysti_verify.h, mv_linearize).
+pub struct Linearized {
+    pub blocks: Vec<u64>, // six words per block, the sub-DAGs one behind the other
+    pub sub: Vec<u64>,    // four per leader: MV_LINEAR_*, first row, count, height
+    pub n_rows: u64,
 }
 
 /// Result of `GpuVerifier::commit_leaders` (layout: include/mysti_verify.h, mv_commit_leaders).
