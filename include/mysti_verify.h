@@ -63,6 +63,9 @@
  *                          BlockStore::linked_to_round (block_store.rs:306-327), and the decided prefix
  *   mv_linearize           Linearizer::handle_commit (consensus/linearizer.rs:125-166): each committed leader's
  *                          sub-DAG in the reference's own order, with the committed marks and last_height
+ *   mv_propose_*           what Core does between add_blocks and new_with_signer: the threshold clock
+ *                          (threshold_clock.rs:58-89), the `pending` queue (core.rs:197-198, 223-224) and the
+ *                          include choice of Core::try_new_block (core.rs:232-278), with the own block's record
  *   mv_seal_blocks         StatementBlock::new_with_signer (types.rs:155-218) on blocks that are bincode
  *                          already: Signer::sign_block (crypto.rs:199-223) over the digest of the signed
  *                          pre-image (crypto.rs:85-128) and BlockDigest::new (crypto.rs:38-61), written
@@ -677,6 +680,85 @@ mv_status mv_linearize_mark(mv_ctx* ctx, const uint64_t* refs /* n x 6 */, uint6
 /* out[0] = the marked references, out[1] = last_height */
 mv_status mv_linearize_stats(mv_ctx* ctx, uint64_t* out /* 2 */);
 
+/* ---- proposing: the threshold clock, the pending queue, the include choice ----
+ * What stands between mv_connect_blocks and mv_seal_blocks in Core (core.rs): the
+ * ThresholdClockAggregator (threshold_clock.rs:37-94), the `pending` queue and the include choice of
+ * Core::try_new_block. Opt-in state on the context's first device, beside the DAG store: the clock
+ * (round, voters, stake), the queue (per entry: include or payload, an include's reference as a slot
+ * of the index and its round, the caller's tag), the own last block (its reference and its includes,
+ * as slots), the choice of a take that mv_propose_own has not confirmed yet, and a stamp per slot of
+ * the index. Without mv_propose_reserve every other call does what it did before, launch for launch,
+ * and every call below is MV_E_INVALID_ARG. mv_index_clear empties the state (clock at round 0, empty
+ * queue, no own block), mv_destroy frees it, a rebuild of the index re-resolves its slots. */
+#define MV_PROPOSE_IN_ORDER 1   /* mv_propose_add: take the rows in the order given */
+#define MV_PROPOSE_PAYLOAD 2    /* mv_propose_add: one payload entry behind the rows */
+#define MV_PROPOSE_INCOMPLETE 1 /* mv_propose_take, out[3]: a taken include of round > 0 has no record */
+#define MV_PROPOSE_SHORT 2      /* mv_propose_take, out[3]: cap or cap_p was too small; nothing was taken */
+/* Opt in for `authority` (a seat of the committee, MV_E_NO_COMMITTEE without one), with room for
+ * `entries` queue entries (never shrinks; the queue grows as needed): the clock of
+ * ThresholdClockAggregator::new(0) (core.rs:88), an empty queue, no own block. */
+mv_status mv_propose_reserve(mv_ctx* ctx, uint32_t authority, uint64_t entries);
+/* The loop of Core::add_blocks over the processed blocks (core.rs:181-200) and the entry of
+ * run_block_handler (core.rs:223-224). rows: n references, words 0-5 of each stride_words words -- the
+ * connected rows of mv_connect_blocks as they are at a stride of 8. They are sorted by round, stably
+ * (core.rs:181-183); each goes through ThresholdClockAggregator::add_block (threshold_clock.rs:58-89)
+ * and joins the queue as an include entry with its tag (the block's WAL position; 0 without tags).
+ *   Less (:61): nothing. Greater (:63-67): the set is cleared, the author added, the round set -- the
+ *   quorum answer of that add is ignored. Equal (:68-87): the author is added, once per round, and
+ *   when StakeAggregator::add answers true (committee.rs:314-320: stake > quorum_threshold, also for an
+ *   author counted before) the set is cleared and the round is the block's + 1.
+ * MV_PROPOSE_IN_ORDER skips the sort: the replay of the recovered `pending` in Core::open
+ * (core.rs:90-94) and its genesis loop (:104-109). With MV_PROPOSE_PAYLOAD one payload entry carrying
+ * payload_token follows the rows (n = 0: that entry alone).
+ * Every row must have an entry in the index and an authority of the committee: otherwise
+ * MV_E_INVALID_ARG, and clock and queue are as they were.
+ * out: 0 the clock round after the call, 1 the aggregator's stake, 2 its voters, 3 the queue's length. */
+mv_status mv_propose_add(mv_ctx* ctx, const uint64_t* rows, uint64_t n, uint64_t stride_words /* >= 6 */,
+                         const uint64_t* tags /* n, may be NULL */, uint32_t flags, uint64_t payload_token,
+                         uint64_t* out /* 4 */);
+/* The include choice of Core::try_new_block (core.rs:232-278). Clock round <= the own last block's
+ * round (:233-235): out[0] = 0, nothing changes. Otherwise
+ *   1. the cut (:240-247) is the first include entry whose round is >= the clock round, else the
+ *      queue's end; the entries before it are taken (:249-251);
+ *   2. references_in_block (:254-263) is the includes of the own last block and of every taken include
+ *      entry's block. The blocks are the DAG store's records; a taken entry without one (a seeded
+ *      genesis reference, a pruned round, a replay row seeded as a reference only) adds nothing, as
+ *      get_block's None does, and unless its round is 0 sets MV_PROPOSE_INCOMPLETE in out[3];
+ *   3. includes (:265-271): the taken include entries that are not in that set, as references, in queue
+ *      order, a reference that was queued twice twice. The own last block is not among them: the
+ *      caller puts it first (:264);
+ *   4. payloads (:272-276): the tokens of the taken payload entries, in queue order;
+ *   5. the entries from the cut on are the queue.
+ * The take is then outstanding until mv_propose_own confirms it; a take while one is outstanding, or
+ * before the first mv_propose_own: MV_E_INVALID_ARG, nothing changes.
+ * *n_includes and *n_payloads are the totals. If one is above its cap nothing is written past the
+ * cap, out[3] has MV_PROPOSE_SHORT, out[0] = 0, and queue and state are as they were: call again with room.
+ * out: 0 proposed (0 / 1), 1 the clock round (the new block's round), 2 the entries taken, 3 the flags,
+ * 4 the tag of the first entry left (UINT64_MAX: none; next_entry, :311-315), 5 the queue's length.
+ * Words 2 to 4 describe the cut, so they are what a take that runs computes: after a refusal for room
+ * (MV_PROPOSE_SHORT) they are what the take would have taken and left, and the queue is whole; when the
+ * clock round is <= the own last block's round no cut is made, and they are 0, 0 and UINT64_MAX
+ * whatever the queue holds. */
+mv_status mv_propose_take(mv_ctx* ctx, uint64_t* includes /* cap x 6 */, uint64_t cap, uint64_t* n_includes,
+                          uint64_t* payloads /* cap_p */, uint64_t cap_p, uint64_t* n_payloads, uint64_t* out /* 6 */);
+/* The own block after it was sealed (core.rs:307-320), and the own genesis block (:110-116). `ref` is
+ * inserted as MV_REF_STORED, goes through add_block on the clock (:307-308, :110), and becomes the own
+ * last block with its includes (:316-319); the outstanding take is dropped. With the DAG store
+ * reserved its record -- slot, authority, round, the includes as slots -- joins the store (unless the
+ * reference has one), so mv_decide_leaders, mv_commit_leaders and mv_linearize see the block; the
+ * n = 0 sweep of mv_connect_blocks for the blocks that waited for it stays the caller's.
+ * includes == NULL: the own last block followed by the outstanding take's choice, which is what the
+ * caller sealed; ref's round must be that take's clock round. An explicit list (k x 6, each in the
+ * index) is for genesis (k = 0, any non-NULL pointer) and for a restart. ref's authority must be the
+ * reserved one. MV_E_INVALID_ARG otherwise, and nothing changes.
+ * out: as mv_propose_add. */
+mv_status mv_propose_own(mv_ctx* ctx, const uint64_t* ref /* 6 */, const uint64_t* includes /* k x 6 or NULL */,
+                         uint64_t k, uint64_t* out /* 4 */);
+/* out: 0 the clock round, 1 the aggregator's stake, 2 its voters, 3 the queue's length, 4 the own last
+ * block's round, 5 a take is outstanding (0 / 1), 6 the takes so far, 7 the include entries the last
+ * take dropped (core.rs:268). */
+mv_status mv_propose_stats(mv_ctx* ctx, uint64_t* out /* 8 */);
+
 /* ---- seeding the DAG store from a replayed WAL ----
  * mv_wal_replay, then one seed call over all its rows while the image is still in device memory:
  * the blocks of a WAL become stored blocks with records, which is what makes a replayed block
@@ -956,6 +1038,13 @@ mv_status mv_dev_commit_leaders(mv_ctx* ctx, int device, const uint64_t* d_leade
  * *n_rows on the host. `stream` is synchronised (the edge counts size the levels' launches). */
 mv_status mv_dev_linearize(mv_ctx* ctx, int device, const uint64_t* d_leaders, uint32_t n, uint64_t* d_blocks,
                            uint64_t cap, uint64_t* d_sub, uint64_t* n_rows, void* stream);
+/* mv_propose_add (core.rs:181-200, 223-224) with the rows, the tags (may be NULL) and the four result
+ * words in HBM of the context's first device: d_rows may be mv_dev_connect_blocks' connected rows as
+ * they are (stride 8). `stream` is synchronised (the rows without a slot decide whether anything
+ * changes, their rounds size the sort). */
+mv_status mv_dev_propose_add(mv_ctx* ctx, int device, const uint64_t* d_rows, uint64_t n, uint64_t stride_words,
+                             const uint64_t* d_tags, uint32_t flags, uint64_t payload_token, uint64_t* d_out /* 4 */,
+                             void* stream);
 /* mv_seal_blocks on blocks already in HBM (new_with_signer as there: types.rs:155-218,
  * crypto.rs:38-61, 199-223): the image is patched in place. Every array is device memory; d_buf is
  * 8-byte aligned with 16 readable bytes past buf_bytes, d_seeds 4-byte and the digest arrays (n x 32,

@@ -42,6 +42,9 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.linearize (and dev_linearize, linearize_mark, linearize_stats)
                            Linearizer::handle_commit (linearizer.rs:125-166): the committed leaders' sub-DAGs in
                            the reference's order, with the committed marks and last_height kept in the engine
+  Engine.propose_reserve, propose_add (and dev_propose_add), propose_take, propose_own, propose_stats
+                           the threshold clock (threshold_clock.rs:58-89), Core's `pending` queue and the include
+                           choice of Core::try_new_block (core.rs:181-278), with the own block's DAG record
   Engine.dev_accept_blocks, Engine.dev_connect_blocks, Engine.dev_index_insert
                            the same on buffers already in HBM (a replay's rows go in at a stride)
   frame_messages           the frame and message walk alone, on the host, for one stream
@@ -84,6 +87,7 @@ EXPORTS = [
     "mv_dag_reserve", "mv_dag_prune", "mv_dag_stats", "mv_decide_leaders", "mv_dev_decide_leaders",
     "mv_commit_leaders", "mv_dev_commit_leaders", "mv_wal_recover", "mv_dev_dag_seed_rows",
     "mv_linearize", "mv_dev_linearize", "mv_linearize_mark", "mv_linearize_stats",
+    "mv_propose_reserve", "mv_propose_add", "mv_dev_propose_add", "mv_propose_take", "mv_propose_own", "mv_propose_stats",
     "mv_seal_blocks", "mv_dev_seal_blocks",
     "mv_votes_reserve", "mv_votes_clear", "mv_votes_stats", "mv_aggregate_votes", "mv_dev_aggregate_votes",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
@@ -125,6 +129,11 @@ COMMIT_NO_ANCHOR = 0xFFFFFFFFFFFFFFFF
 LINEAR_STATUS = ["OK", "INCOMPLETE", "COMMITTED", "OVERFLOW", "STOPPED"]
 LINEAR_OK, LINEAR_INCOMPLETE, LINEAR_COMMITTED, LINEAR_OVERFLOW, LINEAR_STOPPED = range(5)
 LINEAR_MAX_DEPTH, LINEAR_MAX_INCLUDE, LINEAR_MAX_LEADERS = 16, 0xFFFE, 0xFFFF
+# mv_propose_add's flags, the flag bits of mv_propose_take's out[3], its out[4] without an entry left
+PROPOSE_IN_ORDER, PROPOSE_PAYLOAD = 1, 2
+PROPOSE_INCOMPLETE, PROPOSE_SHORT = 1, 2
+PROPOSE_NO_ENTRY = 0xFFFFFFFFFFFFFFFF
+PROPOSE_GUARD = 0xA5A5A5A5A5A5A5A5  # Engine.propose_take: what stands behind cap rows before the call
 WAL_MAP_BITS, WAL_MAP_BITS_TEST = 24, 16  # wal.rs:95-103
 # batch path stages, the block pipeline's, the WAL replay's (mv_stage_times order, MV_NSTAGES)
 STAGES = ["prep", "sort", "bucket", "reduce", "final", "fallback", "parse", "hash", "verify", "verdict", "wal_walk",
@@ -242,6 +251,12 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_linearize.argtypes = [vp, ctypes.c_int, vp, u32, vp, u64, vp, vp, vp]
     lib.mv_linearize_mark.argtypes = [vp, vp, u64, u64]
     lib.mv_linearize_stats.argtypes = [vp, vp]
+    lib.mv_propose_reserve.argtypes = [vp, u32, u64]
+    lib.mv_propose_add.argtypes = [vp, vp, u64, u64, vp, u32, u64, vp]
+    lib.mv_dev_propose_add.argtypes = [vp, ctypes.c_int, vp, u64, u64, vp, u32, u64, vp, vp]
+    lib.mv_propose_take.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp]
+    lib.mv_propose_own.argtypes = [vp, vp, vp, u64, vp]
+    lib.mv_propose_stats.argtypes = [vp, vp]
     lib.mv_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     lib.mv_host_free.argtypes = [vp, vp]
     lib.mv_host_free.restype = None
@@ -1037,6 +1052,76 @@ class Engine:
         self._check(self.lib.mv_linearize_stats(self.ctx, _p(out)), "mv_linearize_stats")
         return LinearStats(int(out[0]), int(out[1]))
 
+    def propose_reserve(self, authority: int, entries: int = 0):
+        """Opts in to the proposer's state for `authority` (mv_propose_reserve): the clock at round 0, an
+        empty queue with room for `entries`."""
+        self._check(self.lib.mv_propose_reserve(self.ctx, int(authority), int(entries)), "mv_propose_reserve")
+
+    def propose_add(self, rows, tags=None, in_order: bool = False, payload: Optional[int] = None) -> "ProposeClock":
+        """Core::add_blocks' loop over the processed blocks (mv_propose_add): rows (n, 6) references or
+        (n, 8) connected rows as connect_blocks gives them, tags (n,) their WAL positions; payload: the
+        token of the payload entry that follows them."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.shape[1] >= 6:
+            rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        else:
+            rows = ref_words(rows)  # (n, 6) words, or (authority, round, digest) tuples
+        n, stride = rows.shape
+        t = None if tags is None else np.ascontiguousarray(np.asarray(tags, dtype=np.uint64))
+        if t is not None and t.shape != (n,):
+            raise ValueError("tags: one word per row")
+        flags = (PROPOSE_IN_ORDER if in_order else 0) | (PROPOSE_PAYLOAD if payload is not None else 0)
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.mv_propose_add(self.ctx, _p(rows) if n else None, n, stride, _p(t) if n else None, flags,
+                                            int(payload or 0), _p(out)), "mv_propose_add")
+        return ProposeClock(*(int(x) for x in out))
+
+    def dev_propose_add(self, device: int, d_rows, d_tags=None, in_order: bool = False, payload: Optional[int] = None,
+                        n: Optional[int] = None, stream_handle: int = 0) -> "ProposeClock":
+        """mv_dev_propose_add on torch device tensors: d_rows (>= n, stride) int64 with stride >= 6 (the
+        first n rows; connected rows as dev_connect_blocks wrote them), d_tags (n,) int64 or None."""
+        import torch
+
+        vp = ctypes.c_void_p
+        n = d_rows.shape[0] if n is None else int(n)
+        flags = (PROPOSE_IN_ORDER if in_order else 0) | (PROPOSE_PAYLOAD if payload is not None else 0)
+        d_out = torch.zeros(4, dtype=torch.int64, device=d_rows.device)
+        self._check(self.lib.mv_dev_propose_add(self.ctx, device, vp(d_rows.data_ptr()), n, d_rows.shape[1],
+                                                vp(d_tags.data_ptr()) if d_tags is not None else None, flags,
+                                                int(payload or 0), vp(d_out.data_ptr()), vp(stream_handle or None)),
+                    "mv_dev_propose_add")
+        return ProposeClock(*(int(x) for x in d_out.cpu().numpy().view(np.uint64)))
+
+    def propose_take(self, cap: int = 1 << 12, cap_payloads: int = 1 << 12) -> "Proposal":
+        """Core::try_new_block's include choice (mv_propose_take): the includes without the own last
+        block, the payload tokens, and the out words."""
+        cap, cap_p = int(cap), int(cap_payloads)
+        # one guard row / word behind each cap: the library writes nothing there (Proposal.guard_intact)
+        inc = np.full((cap + 1, 6), PROPOSE_GUARD, dtype=np.uint64)
+        pay = np.full(cap_p + 1, PROPOSE_GUARD, dtype=np.uint64)
+        out = np.zeros(6, dtype=np.uint64)
+        ni, npay = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.lib.mv_propose_take(self.ctx, _p(inc) if cap else None, cap, ctypes.byref(ni),
+                                             _p(pay) if cap_p else None, cap_p, ctypes.byref(npay), _p(out)),
+                    "mv_propose_take")
+        return Proposal(inc, pay, int(ni.value), int(npay.value), cap, cap_p, out)
+
+    def propose_own(self, ref, includes=None) -> "ProposeClock":
+        """The own block after it was sealed, or the own genesis block (mv_propose_own). includes None:
+        the own last block followed by the outstanding take's choice; else the (k, 6) list, k may be 0."""
+        r = ref_words(ref if isinstance(ref, np.ndarray) else [ref]).reshape(6)
+        inc, k = None, 0
+        if includes is not None:
+            inc = ref_words(includes) if len(includes) else np.zeros((1, 6), dtype=np.uint64)
+            k = len(includes)
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.mv_propose_own(self.ctx, _p(r), _p(inc), k, _p(out)), "mv_propose_own")
+        return ProposeClock(*(int(x) for x in out))
+
+    def propose_stats(self) -> "ProposeStats":
+        out = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.mv_propose_stats(self.ctx, _p(out)), "mv_propose_stats")
+        return ProposeStats(*(int(x) for x in out))
+
     def dev_index_insert(self, device: int, d_words, stride_words: int, n: int, state: int = REF_HAVE,
                          stream_handle: int = 0, word_offset: int = 0):
         """mv_dev_index_insert: reference i is the six int64 words of torch device tensor d_words at
@@ -1300,6 +1385,47 @@ class LinearStats:
 
     def __init__(self, marked, last_height):
         self.marked, self.last_height = marked, last_height
+
+
+class ProposeClock:
+    """Result of Engine.propose_add / propose_own: the clock round after the call, the aggregator's stake
+    and voters, the queue's length."""
+
+    def __init__(self, round, stake, voters, queue):
+        self.round, self.stake, self.voters, self.queue = round, stake, voters, queue
+
+    def words(self):
+        return [self.round, self.stake, self.voters, self.queue]
+
+
+class Proposal:
+    """Result of Engine.propose_take (mv_propose_take): proposed, round (the clock's: the new block's),
+    taken (queue entries), flags (PROPOSE_*), next_entry (the tag of the first entry left,
+    PROPOSE_NO_ENTRY without one), queue (its length); includes (min(n_includes, cap), 6) uint64 without
+    the own last block, payloads the tokens; n_includes and n_payloads are the totals."""
+
+    def __init__(self, inc, pay, n_includes, n_payloads, cap, cap_p, out):
+        self.n_includes, self.n_payloads = n_includes, n_payloads
+        self.includes, self.payloads = inc[:min(n_includes, cap)], pay[:min(n_payloads, cap_p)]
+        # nothing was written past what the call filled, nor past the caps
+        self.guard_intact = bool((inc[min(n_includes, cap):] == PROPOSE_GUARD).all() and
+                                 (pay[min(n_payloads, cap_p):] == PROPOSE_GUARD).all())
+        self.proposed, self.round, self.taken, self.flags, self.next_entry, self.queue = (int(x) for x in out)
+
+    def include_refs(self):
+        """The includes as tuples of six words."""
+        return [tuple(int(w) for w in row) for row in self.includes]
+
+
+class ProposeStats:
+    """Result of Engine.propose_stats (mv_propose_stats)."""
+
+    def __init__(self, round, stake, voters, queue, own_round, outstanding, takes, dropped):
+        self.round, self.stake, self.voters, self.queue = round, stake, voters, queue
+        self.own_round, self.outstanding, self.takes, self.dropped = own_round, outstanding, takes, dropped
+
+    def words(self):
+        return [self.round, self.stake, self.voters, self.queue, self.own_round, self.outstanding, self.takes, self.dropped]
 
 
 class Seeded:

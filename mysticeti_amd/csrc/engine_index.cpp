@@ -61,6 +61,14 @@ mv_status index_resize(mv_ctx* ctx, Device& dev, uint64_t slots, hipStream_t s) 
       HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, d.slot, dg.nb, ix.ctl.as<uint64_t>(), s));
       HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, d.inc, dg.ni, ix.ctl.as<uint64_t>(), s));
     }
+    // ... and the proposer's state
+    if (ix.prop.on) {
+      st = propose_follow_table(ctx, dev, old_slots, nt, s);
+      if (st != MV_OK) {
+        (void)hipStreamSynchronize(s);
+        return st;
+      }
+    }
   }
   // its slot -> record map is as long as the table: a fresh one, filled from the re-resolved slots
   DevBuf fresh_map;
@@ -376,6 +384,10 @@ mv_status mv_index_clear(mv_ctx* ctx) {
   ix.pend.nb = ix.pend.ni = ix.pend.levels = 0;  // the store's records are slots of the table
   ix.dag.nb = ix.dag.ni = 0;                     // ... and so are the DAG store's
   ix.dag.lin_marked = ix.dag.lin_height = 0;     // ... and the linearizer's marks
+  if (ix.prop.on) {                              // ... and the proposer's queue, own block and choice
+    st = propose_clear(ctx, *dev, dev->stream);
+    if (st != MV_OK) return st;
+  }
   if (!ix.slots) return MV_OK;
   if (ix.dag.on && ix.dag.map_slots) {
     HIPCHK(ctx, hipMemsetAsync(ix.dag.map.p, 0xff, 4 * (size_t)ix.dag.map_slots, dev->stream));

@@ -2,7 +2,7 @@
 // error plumbing, the sharding helpers, and the declarations of the functions that cross files
 // (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp,
 // engine_index.cpp, engine_connect.cpp, engine_dag.cpp, engine_decide.cpp, engine_linearize.cpp,
-// engine_seal.cpp, engine_votes.cpp).
+// engine_propose.cpp, engine_seal.cpp, engine_votes.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -211,6 +211,27 @@ struct Device {
       uint64_t lin_marked = 0, lin_height = 0;
       DevBuf lctl, llead, lbest, lnode, lbk, ledge, lres;
     } dag;
+    // mv_propose_*: the proposer's state (propose.hip), made by mv_propose_reserve only -- the clock in
+    // the control words ctl (mvk::PP_CTL_*), the queue in two copies (kind | slot | round | tag for
+    // cap entries) of which `cur` is in force, the own last block (own[own_cur]: its slot, then own_k
+    // include slots; mv_propose_own fills the other copy and flips), the outstanding choice (slots), and a stamp per slot of the table. Slots are those of the
+    // table in force: a rebuild re-resolves them and the stamps are remade for the next take.
+    struct Propose {
+      bool on = false;
+      uint32_t authority = 0;
+      DevBuf ctl, q[2], own[2], choice, stamp;
+      int cur = 0, own_cur = 0;
+      uint64_t qn = 0, cap = 0;
+      bool has_own = false, outstanding = false;
+      uint64_t round = 0;  // the clock round as of the last call (the control words', read back)
+      uint64_t own_round = 0, own_k = 0, n_choice = 0, take_round = 0;
+      uint64_t stamp_slots = 0;
+      uint32_t counter = 0;
+      uint64_t takes = 0, dropped = 0;
+      // a call's scratch: per row slot | round | tag (u64), auth | sauth | perm x 2 | seglen | pos0 | pos1
+      // (u32), first (u8), stot (u64); the results of a take; the staged rows
+      DevBuf rows, res, in;
+    } prop;
   } index;
 
   // mv_seal_blocks (seal.hip): the expanded keys, the scan's heads, the link table, both digest
@@ -533,6 +554,13 @@ mv_status dag_seed_run(mv_ctx* ctx, Device& dev, const uint8_t* d_img, uint64_t 
 // caller swaps it into dg.lmark once s has been synchronised.
 mv_status linear_marks_for(mv_ctx* ctx, Device& dev, uint64_t old_slots, const mvk::IndexTable& nt, uint64_t slots,
                            DevBuf& fresh, hipStream_t s);
+
+// engine_propose.cpp: the proposer's state follows the table -- its slots (queue, own last block,
+// outstanding choice) of the table in force (old_slots of them) become those of the same keys under
+// the new table nt, on s; the stamps are remade by the next take. And mv_index_clear's part.
+using Propose = Device::Index::Propose;
+mv_status propose_follow_table(mv_ctx* ctx, Device& dev, uint64_t old_slots, const mvk::IndexTable& nt, hipStream_t s);
+mv_status propose_clear(mv_ctx* ctx, Device& dev, hipStream_t s);
 
 // engine_online.cpp
 bool online_eligible(mv_ctx* ctx, uint32_t n, uint64_t bytes, uint64_t longest);

@@ -761,6 +761,87 @@ hipError_t launch_linear_mark(const uint64_t* item, uint64_t n, uint32_t* mark, 
 hipError_t launch_linear_carry(const uint64_t* old_slots, uint64_t n_old, const uint32_t* old_mark, const IndexTable& t,
                                uint32_t* mark, uint64_t* ctl, hipStream_t s);
 
+// propose.hip: mv_propose_* (the threshold clock, the pending queue and the include choice of
+// Core::add_blocks / try_new_block, core.rs:181-278). The control words of the state (device, u64):
+// the clock -- round, stake, voters, the voters bitmap (DG_BM_WORDS u32 words in PP_CTL_BM..) -- and
+// a call's words: rows without a slot, the OR of the rows' rounds and of their complements (a bit set in
+// both differs over the call), the zeros of a sort
+// pass, the cut, the includes and payloads kept, the include entries taken, the flags, the tag of the
+// first entry behind the cut, whether the own record was appended.
+constexpr int PP_CTL_ROUND = 0, PP_CTL_STAKE = 1, PP_CTL_VOTERS = 2, PP_CTL_BM = 3, PP_CTL_NMISS = PP_CTL_BM + DG_BM_WORDS / 2,
+              PP_CTL_OR = PP_CTL_NMISS + 1, PP_CTL_NOR = PP_CTL_NMISS + 2, PP_CTL_ZEROS = PP_CTL_NMISS + 3,
+              PP_CTL_CUT = PP_CTL_NMISS + 4, PP_CTL_NINC = PP_CTL_NMISS + 5, PP_CTL_NPAY = PP_CTL_NMISS + 6,
+              PP_CTL_NENT = PP_CTL_NMISS + 7, PP_CTL_FLAGS = PP_CTL_NMISS + 8, PP_CTL_NEXT = PP_CTL_NMISS + 9,
+              PP_CTL_APPENDED = PP_CTL_NMISS + 10, PP_CTL_WORDS = PP_CTL_NMISS + 13;
+constexpr uint32_t PP_INCLUDE = 1, PP_PAYLOAD = 2;  // an entry's kind
+// The queue, entries in arrival order: kind, the slot of an include's reference (DG_NO_SLOT for a
+// payload), its round, the caller's tag. The engine keeps two copies; a take moves the tail into the other.
+struct PropQueue {
+  uint32_t* kind;
+  uint64_t* slot;
+  uint64_t* round;
+  uint64_t* tag;
+};
+// The rows of one clock step, in the order the automaton takes them, and the per-row scratch of the
+// batch form: first (the row is the first of its author in its segment of equal round), and at a
+// segment's first row its length, the first row at which the stake of first-seen authors passes the
+// quorum (pos0; pos1: the first such row behind the segment's first; DG_NONE: none) and the stake of
+// all its authors.
+struct PropClock {
+  const uint64_t* round;
+  const uint32_t* auth;
+  uint64_t n;
+  uint8_t* first;
+  uint32_t* seglen;
+  uint32_t* pos0;
+  uint32_t* pos1;
+  uint64_t* stot;
+  const uint64_t* stakes;
+  uint32_t n_auth;
+  uint64_t quorum;  // quorum <=> stake > it
+};
+// a lane per row: slot[i] of its key (a probe; none, or an authority outside the committee: pctl[PP_CTL_NMISS]),
+// round[i], auth[i]; pctl[PP_CTL_OR / _NOR] their rounds' bits; perm[i] = i
+hipError_t launch_propose_resolve(const IndexTable& t, const uint64_t* rows, uint64_t n, uint64_t stride_words, uint32_t n_auth,
+                                  uint64_t* slot, uint64_t* round, uint32_t* auth, uint32_t* perm, uint64_t* pctl,
+                                  uint64_t* ctl, hipStream_t s);
+// one pass of a stable sort of perm by bit `bit` of round[perm[i]]: count, scan, scatter
+hipError_t launch_propose_sort_bit(const uint64_t* round, int bit, const uint32_t* perm, uint32_t* perm_out,
+                                   uint64_t n, uint64_t* wg, uint64_t* pctl, hipStream_t s);
+// entry q0 + j of the queue = row perm[j] (an include with tags[perm[j]], 0 without tags), sauth[j] its
+// authority; with `payload` one payload entry carrying `token` behind them
+hipError_t launch_propose_append(const uint64_t* slot, const uint64_t* round, const uint32_t* auth, const uint64_t* tags,
+                                 const uint32_t* perm, uint64_t n, const PropQueue& q, uint64_t q0, uint64_t qcap,
+                                 uint32_t* sauth, bool payload, uint64_t token, uint64_t* ctl, hipStream_t s);
+// ThresholdClockAggregator::add_block over the rows of c, in order: the segment scan (a wave per
+// segment), then the chain over the segments (one wave); pctl's clock words before and after
+hipError_t launch_propose_clock(const PropClock& c, uint64_t* pctl, uint64_t* ctl, hipStream_t s);
+// pctl[PP_CTL_CUT] = the first include entry of round >= `round` (qn without one)
+hipError_t launch_propose_cut(const PropQueue& q, uint64_t qn, uint64_t round, uint64_t* pctl, hipStream_t s);
+// stamp[include slot] = counter for the includes of the records of the include entries before `cut`
+// and for the own last block's n_own includes; an entry of round > 0 without a record: MV_PROPOSE_INCOMPLETE
+hipError_t launch_propose_stamp(const PropQueue& q, uint64_t cut, const DagStore& d, uint64_t nb, bool dag_on,
+                                const uint64_t* own_inc, uint64_t n_own, uint32_t* stamp, uint64_t n_stamp, uint32_t counter,
+                                uint64_t* pctl, uint64_t* ctl, hipStream_t s);
+// the include entries before `cut` whose slot is not stamped, as references (cap x 6) and as slots
+// (choice, cap_choice), and the payload tokens (cap_p), all in queue order; the totals and the next tag
+hipError_t launch_propose_keep(const IndexTable& t, const PropQueue& q, uint64_t qn, uint64_t cut, const uint32_t* stamp,
+                               uint64_t n_stamp, uint32_t counter, uint64_t* includes, uint64_t cap, uint64_t* choice,
+                               uint64_t cap_choice, uint64_t* payloads, uint64_t cap_p, uint64_t* wg, uint64_t* pctl,
+                               uint64_t* ctl, hipStream_t s);
+// the entries [cut, qn) of q become the entries [0, qn - cut) of to
+hipError_t launch_propose_shift(const PropQueue& q, const PropQueue& to, uint64_t cut, uint64_t qn, hipStream_t s);
+// own_out = the slot of the insert's item 0, then the includes: `prev` (the own last block's slot, with has_prev)
+// and the n_src slots of src
+hipError_t launch_propose_own(const uint64_t* item, const uint64_t* prev, bool has_prev, const uint64_t* src, uint64_t n_src,
+                              uint64_t* own_out, uint64_t n_slots, uint64_t* ctl, hipStream_t s);
+// the own block's record behind d's nb records and ni includes, unless its slot has one: pctl[PP_CTL_APPENDED]
+hipError_t launch_propose_record(const IndexTable& t, const DagStore& d, uint64_t nb, uint64_t ni, const uint64_t* own,
+                                 uint64_t k, uint64_t* pctl, uint64_t* ctl, hipStream_t s);
+// after launch_index_rebuild: as launch_pend_reresolve, for n slot numbers of which some are DG_NO_SLOT
+hipError_t launch_propose_reresolve(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* slotidx,
+                                    uint64_t n, uint64_t* ctl, hipStream_t s);
+
 // seal.hip: mv_seal_blocks (StatementBlock::new_with_signer on bincode blocks with placeholder
 // digest and signature fields). keys: 24 words per authority (a mod l, prefix, public key).
 hipError_t launch_seal_keys(const uint8_t* seeds, uint32_t n_auth, const void* btab, uint32_t* keys, hipStream_t s);

@@ -56,6 +56,10 @@ pub const MV_LINEAR_STOPPED: u64 = 4;
 pub const MV_LINEAR_MAX_DEPTH: u64 = 16;
 pub const MV_LINEAR_MAX_INCLUDE: u64 = 65534;
 pub const MV_LINEAR_MAX_LEADERS: u64 = 65535;
+pub const MV_PROPOSE_IN_ORDER: u32 = 1;
+pub const MV_PROPOSE_PAYLOAD: u32 = 2;
+pub const MV_PROPOSE_INCOMPLETE: u64 = 1;
+pub const MV_PROPOSE_SHORT: u64 = 2;
 
 pub const MV_SIG_OK: u8 = 0;
 pub const MV_SIG_INVALID: u8 = 1;
@@ -197,6 +201,16 @@ extern "C" {
                             d_sub: *mut u64, n_rows: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_linearize_mark(ctx: *mut mv_ctx, refs: *const u64, n: u64, height: u64) -> i32;
     pub fn mv_linearize_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
+    pub fn mv_propose_reserve(ctx: *mut mv_ctx, authority: u32, entries: u64) -> i32;
+    pub fn mv_propose_add(ctx: *mut mv_ctx, rows: *const u64, n: u64, stride_words: u64, tags: *const u64, flags: u32,
+                          payload_token: u64, out: *mut u64) -> i32;
+    pub fn mv_dev_propose_add(ctx: *mut mv_ctx, device: i32, d_rows: *const u64, n: u64, stride_words: u64,
+                              d_tags: *const u64, flags: u32, payload_token: u64, d_out: *mut u64,
+                              stream: *mut c_void) -> i32;
+    pub fn mv_propose_take(ctx: *mut mv_ctx, includes: *mut u64, cap: u64, n_includes: *mut u64, payloads: *mut u64,
+                           cap_p: u64, n_payloads: *mut u64, out: *mut u64) -> i32;
+    pub fn mv_propose_own(ctx: *mut mv_ctx, block_ref: *const u64, includes: *const u64, k: u64, out: *mut u64) -> i32;
+    pub fn mv_propose_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
     pub fn mv_dev_index_insert(ctx: *mut mv_ctx, device: i32, d_words: *const u64, stride_words: u64, n: u64,
                                state: u32, stream: *mut c_void) -> i32;
     pub fn mv_dev_dag_seed_rows(ctx: *mut mv_ctx, device: i32, d_wal: *const u8, size: u64, d_blk_rows: *const u64,

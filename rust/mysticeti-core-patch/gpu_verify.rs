@@ -400,6 +400,79 @@ impl GpuVerifier {
         ensure!(rc == sys::MV_OK, "mv_linearize_stats: {}", self.last_error());
         Ok((out[0], out[1]))
     }
+
+    /// Opts in to the proposer's state for `authority` (mv_propose_reserve): the clock of
+    /// ThresholdClockAggregator::new(0), an empty `pending` queue with room for `entries`.
+    pub fn propose_reserve(&self, authority: u32, entries: u64) -> eyre::Result<()> {
+        let rc = unsafe { sys::mv_propose_reserve(self.ctx, authority, entries) };
+        ensure!(rc == sys::MV_OK, "mv_propose_reserve: {}", self.last_error());
+        Ok(())
+    }
+
+    /// The loop of Core::add_blocks (core.rs:181-200) over `rows` (`stride` words each, the reference
+    /// in words 0-5: `Connected::connected` at a stride of 8) with their WAL positions `tags`, and with
+    /// `payload` the entry of run_block_handler (core.rs:223-224). `in_order` skips the sort by round
+    /// (Core::open's replay, core.rs:90-94, 104-109). Returns (clock round, stake, voters, queue length).
+    pub fn propose_add(&self, rows: &[u64], stride: usize, tags: Option<&[u64]>, in_order: bool,
+                       payload: Option<u64>) -> eyre::Result<[u64; 4]> {
+        ensure!(stride >= 6 && rows.len() % stride == 0, "propose_add: rows of {stride} words");
+        let n = rows.len() / stride;
+        ensure!(tags.map_or(true, |t| t.len() == n), "propose_add: one tag per row");
+        let flags = if in_order { sys::MV_PROPOSE_IN_ORDER } else { 0 } | if payload.is_some() { sys::MV_PROPOSE_PAYLOAD } else { 0 };
+        let mut out = [0u64; 4];
+        let rc = unsafe {
+            sys::mv_propose_add(self.ctx, rows.as_ptr(), n as u64, stride as u64, tags.map_or(std::ptr::null(), |t| t.as_ptr()),
+                                flags, payload.unwrap_or(0), out.as_mut_ptr())
+        };
+        ensure!(rc == sys::MV_OK, "mv_propose_add: {}", self.last_error());
+        Ok(out)
+    }
+
+    /// The include choice of Core::try_new_block (core.rs:232-278) (mv_propose_take). The own last
+    /// block is not among the includes: the caller puts it first (:264).
+    pub fn propose_take(&self, cap: usize, cap_payloads: usize) -> eyre::Result<Proposal> {
+        let mut p = Proposal { includes: vec![0u64; 6 * cap.max(1)], payloads: vec![0u64; cap_payloads.max(1)], out: [0u64; 6] };
+        let (mut ni, mut np) = (0u64, 0u64);
+        let rc = unsafe {
+            sys::mv_propose_take(self.ctx, p.includes.as_mut_ptr(), cap as u64, &mut ni, p.payloads.as_mut_ptr(),
+                                 cap_payloads as u64, &mut np, p.out.as_mut_ptr())
+        };
+        ensure!(rc == sys::MV_OK, "mv_propose_take: {}", self.last_error());
+        p.includes.truncate(6 * (ni as usize).min(cap));
+        p.payloads.truncate((np as usize).min(cap_payloads));
+        Ok(p)
+    }
+
+    /// The own block after it was sealed (core.rs:307-320) (mv_propose_own); `includes` None: the own
+    /// last block followed by the outstanding take's choice. Returns as `propose_add`.
+    pub fn propose_own(&self, block_ref: &[u64; 6], includes: Option<&[[u64; 6]]>) -> eyre::Result<[u64; 4]> {
+        let flat: Vec<u64> = includes.map_or(vec![], |i| i.iter().flatten().copied().collect());
+        let mut out = [0u64; 4];
+        let dummy = [0u64; 6];
+        let ptr = match includes {
+            None => std::ptr::null(),
+            Some(i) if i.is_empty() => dummy.as_ptr(),
+            Some(_) => flat.as_ptr(),
+        };
+        let rc = unsafe { sys::mv_propose_own(self.ctx, block_ref.as_ptr(), ptr, includes.map_or(0, |i| i.len()) as u64, out.as_mut_ptr()) };
+        ensure!(rc == sys::MV_OK, "mv_propose_own: {}", self.last_error());
+        Ok(out)
+    }
+
+    /// (clock round, stake, voters, queue length, own last round, outstanding, takes, dropped) (mv_propose_stats)
+    pub fn propose_stats(&self) -> eyre::Result<[u64; 8]> {
+        let mut out = [0u64; 8];
+        let rc = unsafe { sys::mv_propose_stats(self.ctx, out.as_mut_ptr()) };
+        ensure!(rc == sys::MV_OK, "mv_propose_stats: {}", self.last_error());
+        Ok(out)
+    }
+}
+
+/// Result of `GpuVerifier::propose_take` (layout: include/mysti_verify.h, mv_propose_take).
+pub struct Proposal {
+    pub includes: Vec<u64>, // six words per reference, in queue order, without the own last block
+    pub payloads: Vec<u64>, // the tokens of the taken payload entries
+    pub out: [u64; 6],      // proposed, the clock round, entries taken, MV_PROPOSE_* flags, next_entry, queue length
 }
 
 /// Result of `GpuVerifier::linearize` (layout: include/mysti_verify.h, mv_linearize).
