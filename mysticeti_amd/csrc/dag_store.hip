@@ -4,8 +4,9 @@
 // table size and every record number against the store's count before it is an address; a number
 // out of range counts into the error word (MV_E_HIP) and is not followed.
 //   k_dg_app_*   a connect call's rows join the store: records (and map[]), the scan of their
-//                include counts, the include slots a wave per row
-//   k_dg_keep_*  mv_dag_prune: k_pb_keep_*'s shape over "round >= floor"
+//                include counts (AppendBases, a compaction pass of index_dev.h), the include slots
+//                a wave per row
+//   KeepRecords, k_dg_keep_inc   mv_dag_prune: pending.hip's KeepPending over "round >= floor"
 //   k_sd_*       mv_dev_dag_seed_rows: the rows of a replay become stored blocks with records (below)
 #include "index_dev.h"
 
@@ -35,24 +36,19 @@ __global__ void __launch_bounds__(WG) k_dg_app_rows(const u64* __restrict__ slot
   }
   wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
 }
+// where each row's includes start: the scan of the rows' include counts
 // (src[r] is IX_NO_SRC for a row k_dg_app_rows refused: its record is not read)
-__device__ inline uint64_t app_kc(const DagStore& d, uint64_t nb0, uint64_t rows, const uint64_t* src, uint64_t r) {
-  return r < rows && src[r] != mvk::IX_NO_SRC ? d.kc[nb0 + r] : 0;
-}
-__global__ void __launch_bounds__(WG) k_dg_app_count(DagStore d, uint64_t nb0, uint64_t rows, const uint64_t* __restrict__ src,
-                                                     uint64_t* __restrict__ wgcount) {
-  const uint64_t r = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  (void)wg_excl(app_kc(d, nb0, rows, src, r), &tot);
-  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(WG) k_dg_app_list(DagStore d, uint64_t nb0, uint64_t ni0, uint64_t rows,
-                                                    const uint64_t* __restrict__ src, const uint64_t* __restrict__ wgbase) {
-  const uint64_t r = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  const uint64_t ib = ni0 + wgbase[blockIdx.x] + wg_excl(app_kc(d, nb0, rows, src, r), &tot);
-  if (r < rows && src[r] != mvk::IX_NO_SRC) d.ibase[nb0 + r] = ib;
-}
+struct AppendBases {
+  static constexpr int WEIGHTS = 1;
+  DagStore d;
+  uint64_t nb0, ni0, rows;
+  const uint64_t* src;
+  __device__ bool has(uint64_t r) const { return r < rows && src[r] != mvk::IX_NO_SRC; }
+  __device__ void weigh(uint64_t r, uint64_t* kc) const { *kc = has(r) ? d.kc[nb0 + r] : 0; }
+  __device__ void place(uint64_t r, uint64_t, uint64_t ib) const {
+    if (has(r)) d.ibase[nb0 + r] = ni0 + ib;
+  }
+};
 __global__ void __launch_bounds__(WG) k_dg_app_inc(PendStore p, uint64_t nb, DagStore d, uint64_t nb0, uint64_t rows,
                                                    const uint64_t* __restrict__ src, u64* __restrict__ ctl) {
   const uint64_t r = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // a wave per row
@@ -80,59 +76,45 @@ __global__ void __launch_bounds__(WG) k_dg_map(DagStore d, uint64_t nb, u64* __r
   wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
 }
 
-__device__ inline bool dag_keep(const DagStore& d, uint64_t nb, uint64_t floor, uint64_t b, uint32_t* kc) {
-  const bool keep = b < nb && d.round[b] >= floor;
-  *kc = keep ? d.kc[b] : 0;
-  return keep;
-}
-__global__ void __launch_bounds__(WG) k_dg_keep_count(DagStore d, uint64_t nb, uint64_t floor, uint64_t* __restrict__ wg_a,
-                                                      uint64_t* __restrict__ wg_b) {
-  const uint64_t b = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint32_t kc;
-  const bool keep = dag_keep(d, nb, floor, b, &kc);
-  uint64_t tb, tk;
-  (void)wg_excl(keep, &tb);
-  (void)wg_excl(kc, &tk);
-  if (threadIdx.x == 0) {
-    wg_a[blockIdx.x] = tb;
-    wg_b[blockIdx.x] = tk;
+// the records of round >= floor stay, in order; weights: the record, its includes
+struct KeepRecords {
+  static constexpr int WEIGHTS = 2;
+  DagStore d, q;
+  uint64_t nb, floor;
+  uint64_t* newbase;
+  u64* ctl;
+  __device__ void weigh(uint64_t b, uint64_t* keep, uint64_t* kc) const {
+    *keep = b < nb && d.round[b] >= floor;
+    *kc = *keep ? d.kc[b] : 0;
   }
-}
-__global__ void __launch_bounds__(WG) k_dg_keep_list(DagStore d, DagStore q, uint64_t nb, uint64_t floor,
-                                                     const uint64_t* __restrict__ base_a, const uint64_t* __restrict__ base_b,
-                                                     uint64_t* __restrict__ newbase, u64* __restrict__ ctl) {
-  const uint64_t b = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint32_t kc;
-  bool keep = dag_keep(d, nb, floor, b, &kc);
-  uint64_t tb, tk;
-  const uint64_t rb = base_a[blockIdx.x] + wg_excl(keep, &tb);
-  const uint64_t ib = base_b[blockIdx.x] + wg_excl(kc, &tk);
-  bool bad = false;
-  if (b < nb) {
-    const uint64_t s = keep ? d.slot[b] : 0;
-    bad = keep && (rb >= q.cap_b || ib > q.cap_i || kc > q.cap_i - ib || s >= q.n_slots);
-    keep = keep && !bad;
-    newbase[b] = keep ? ib : mvk::IX_NO_SRC;
-    if (keep) {
-      const uint64_t rd = d.round[b];
-      q.slot[rb] = s;
-      q.auth[rb] = d.auth[b];
-      q.round[rb] = rd;
-      q.ibase[rb] = ib;
-      q.kc[rb] = kc;
-      q.map[s] = (uint32_t)rb;
-      atomicMax(ctl + mvk::IX_CTL_DG_NLO, ~rd);
-      atomicMax(ctl + mvk::IX_CTL_DG_HI, rd);
+  __device__ void place(uint64_t b, uint64_t kept, uint64_t rb, uint64_t kc, uint64_t ib) const {
+    bool keep = kept, bad = false;
+    if (b < nb) {
+      const uint64_t s = keep ? d.slot[b] : 0;
+      bad = keep && (rb >= q.cap_b || ib > q.cap_i || kc > q.cap_i - ib || s >= q.n_slots);
+      keep = keep && !bad;
+      newbase[b] = keep ? ib : mvk::IX_NO_SRC;
+      if (keep) {
+        const uint64_t rd = d.round[b];
+        q.slot[rb] = s;
+        q.auth[rb] = d.auth[b];
+        q.round[rb] = rd;
+        q.ibase[rb] = ib;
+        q.kc[rb] = (uint32_t)kc;
+        q.map[s] = (uint32_t)rb;
+        atomicMax(ctl + mvk::IX_CTL_DG_NLO, ~rd);
+        atomicMax(ctl + mvk::IX_CTL_DG_HI, rd);
+      }
     }
+    wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
   }
-  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
-}
+};
 __global__ void __launch_bounds__(WG) k_dg_keep_inc(DagStore d, DagStore q, uint64_t nb, const uint64_t* __restrict__ newbase) {
   const uint64_t b = ((uint64_t)blockIdx.x * WG + threadIdx.x) / 64;  // a wave per record
   if (b >= nb || newbase[b] == mvk::IX_NO_SRC) return;
   const uint64_t from = d.ibase[b], to = newbase[b];
   const uint32_t kc = d.kc[b];
-  if (from > d.cap_i || kc > d.cap_i - from) return;  // (k_dg_keep_list checked the other side)
+  if (from > d.cap_i || kc > d.cap_i - from) return;  // (KeepRecords checked the other side)
   for (uint32_t i = threadIdx.x & 63; i < kc; i += 64) q.inc[to + i] = d.inc[from + i];
 }
 
@@ -315,15 +297,12 @@ hipError_t launch_dag_append(const IndexTable& t, const PendStore& p, uint64_t n
                              const uint32_t* row_of, uint64_t rows, const DagStore& d, uint64_t nb0, uint64_t ni0,
                              uint64_t* src, uint64_t* wg, uint64_t* ctl, hipStream_t s) {
   if (rows == 0 || nb == 0) return hipSuccess;
-  const WgScan w = wg_scan_of(wg, rows);
-  const dim3 gr(grid_of(rows)), b(WG);
+  const dim3 b(WG);
   hipError_t e = hipMemsetAsync(src, 0xff, 8 * rows, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_dg_app_rows, dim3(grid_of(nb)), b, 0, s, (const u64*)t.slots, p, nb, lvl, row_of, rows, d, nb0, src,
                      (u64*)ctl);
-  hipLaunchKernelGGL(k_dg_app_count, gr, b, 0, s, d, nb0, rows, src, w.count_a);
-  (void)launch_index_scan(w.count_a, index_groups(rows), w.base_a, ctl + IX_CTL_DG_NI, nullptr, s);
-  hipLaunchKernelGGL(k_dg_app_list, gr, b, 0, s, d, nb0, ni0, rows, src, w.base_a);
+  compact_pass(AppendBases{d, nb0, ni0, rows, src}, rows, wg_scan_of(wg, rows), ctl + IX_CTL_DG_NI, nullptr, nullptr, s);
   hipLaunchKernelGGL(k_dg_app_inc, dim3(grid_of(64 * rows)), b, 0, s, p, nb, d, nb0, rows, src, (u64*)ctl);
   return hipGetLastError();
 }
@@ -339,16 +318,11 @@ hipError_t launch_dag_map(const DagStore& d, uint64_t nb, uint64_t* ctl, hipStre
 hipError_t launch_dag_prune(const DagStore& d, const DagStore& q, uint64_t nb, uint64_t floor, uint64_t* newbase,
                             uint64_t* wg, uint64_t* ctl, hipStream_t s) {
   if (nb == 0) return hipSuccess;
-  const uint64_t nwg = index_groups(nb);
-  const WgScan w = wg_scan_of(wg, nb);
-  const dim3 g(grid_of(nb)), b(WG);
   hipError_t e = hipMemsetAsync(q.map, 0xff, 4 * q.n_slots, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_dg_keep_count, g, b, 0, s, d, nb, floor, w.count_a, w.count_b);
-  (void)launch_index_scan(w.count_a, nwg, w.base_a, ctl + IX_CTL_DG_NB, nullptr, s);
-  (void)launch_index_scan(w.count_b, nwg, w.base_b, ctl + IX_CTL_DG_NI, nullptr, s);
-  hipLaunchKernelGGL(k_dg_keep_list, g, b, 0, s, d, q, nb, floor, w.base_a, w.base_b, newbase, (u64*)ctl);
-  hipLaunchKernelGGL(k_dg_keep_inc, dim3(grid_of(64 * nb)), b, 0, s, d, q, nb, newbase);
+  compact_pass(KeepRecords{d, q, nb, floor, newbase, (u64*)ctl}, nb, wg_scan_of(wg, nb), ctl + IX_CTL_DG_NB, ctl + IX_CTL_DG_NI,
+               nullptr, s);
+  hipLaunchKernelGGL(k_dg_keep_inc, dim3(grid_of(64 * nb)), dim3(WG), 0, s, d, q, nb, newbase);
   return hipGetLastError();
 }
 

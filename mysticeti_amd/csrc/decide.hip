@@ -3,9 +3,9 @@
 // (base_committer.rs:228-357; the wording of every predicate is the header's). The memory model is
 // index_dev.h's; inside one wave, k_dg_cert collects a bitmap in LDS under wave-scope fences. Every
 // slot and record number is checked against the table size and the store's count before it is an address.
-//   k_dg_pick_*  a lane per record: is it a voting (r + 1) or a decision (r + 2) record of a leader
-//                round, by binary search over the sorted distinct rounds; count / scan / list into
-//                vlist and dlist; a leader block adds itself to its rows' candidates
+//   PickRoles    a lane per record: is it a voting (r + 1) or a decision (r + 2) record of a leader
+//                round, by binary search over the sorted distinct rounds; a compaction pass of
+//                index_dev.h into vlist and dlist; a leader block adds itself to its rows' candidates
 //   k_dg_vote    a wave per (voting record, row of that round): any include of the authority, the
 //                first (authority, round) include in include order across batches of 64
 //   k_dg_cert    a wave per (decision record, row): the vote authors among its includes per candidate
@@ -28,48 +28,34 @@ __device__ inline bool leader_group(const DecideIn& in, uint64_t round, uint64_t
   *g = lo;
   return lo < in.ng && in.g_round[lo] == round;
 }
-__device__ inline void pick_roles(const DagStore& d, uint64_t nb, const DecideIn& in, uint64_t rec, bool* voting,
-                                  bool* decision) {
-  uint64_t g;
-  const uint64_t rd = rec < nb ? d.round[rec] : 0;
-  *voting = rec < nb && rd >= 1 && leader_group(in, rd - 1, &g);
-  *decision = rec < nb && rd >= 2 && leader_group(in, rd - 2, &g);
-}
-__global__ void __launch_bounds__(WG) k_dg_pick_count(DagStore d, uint64_t nb, DecideIn in, uint64_t* __restrict__ wg_a,
-                                                      uint64_t* __restrict__ wg_b) {
-  const uint64_t rec = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  bool v, c;
-  pick_roles(d, nb, in, rec, &v, &c);
-  uint64_t tv, tc;
-  (void)wg_excl(v, &tv);
-  (void)wg_excl(c, &tc);
-  if (threadIdx.x == 0) {
-    wg_a[blockIdx.x] = tv;
-    wg_b[blockIdx.x] = tc;
+struct PickRoles {
+  static constexpr int WEIGHTS = 2;
+  DagStore d;
+  uint64_t nb;
+  DecideIn in;
+  DecideState st;
+  __device__ void weigh(uint64_t rec, uint64_t* voting, uint64_t* decision) const {
+    uint64_t g;
+    const uint64_t rd = rec < nb ? d.round[rec] : 0;
+    *voting = rec < nb && rd >= 1 && leader_group(in, rd - 1, &g);
+    *decision = rec < nb && rd >= 2 && leader_group(in, rd - 2, &g);
   }
-}
-__global__ void __launch_bounds__(WG) k_dg_pick_list(DagStore d, uint64_t nb, DecideIn in, DecideState st,
-                                                     const uint64_t* __restrict__ base_a, const uint64_t* __restrict__ base_b) {
-  const uint64_t rec = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  bool v, c;
-  pick_roles(d, nb, in, rec, &v, &c);
-  uint64_t tv, tc;
-  const uint64_t pv = base_a[blockIdx.x] + wg_excl(v, &tv);
-  const uint64_t pc = base_b[blockIdx.x] + wg_excl(c, &tc);
-  if (rec >= nb) return;
-  st.vpos[rec] = v && pv < nb ? (uint32_t)pv : DG_NONE;
-  if (v && pv < nb) st.vlist[pv] = (uint32_t)rec;
-  if (c && pc < nb) st.dlist[pc] = (uint32_t)rec;
-  uint64_t g;
-  if (!leader_group(in, d.round[rec], &g)) return;
-  // a leader block of every row (authority, round) that names it; bounded by the rows of the round
-  const uint64_t a = d.auth[rec], hi = in.g_start[g + 1] < in.n ? in.g_start[g + 1] : in.n;
-  for (uint64_t k = in.g_start[g]; k < hi; k++) {
-    if (in.l_auth[k] != a) continue;
-    const uint32_t at = atomicAdd(st.cand_n + k, 1u);
-    if (at < DG_CAND) st.cand_slot[DG_CAND * k + at] = d.slot[rec];
+  __device__ void place(uint64_t rec, uint64_t v, uint64_t pv, uint64_t c, uint64_t pc) const {
+    if (rec >= nb) return;
+    st.vpos[rec] = v && pv < nb ? (uint32_t)pv : DG_NONE;
+    if (v && pv < nb) st.vlist[pv] = (uint32_t)rec;
+    if (c && pc < nb) st.dlist[pc] = (uint32_t)rec;
+    uint64_t g;
+    if (!leader_group(in, d.round[rec], &g)) return;
+    // a leader block of every row (authority, round) that names it; bounded by the rows of the round
+    const uint64_t a = d.auth[rec], hi = in.g_start[g + 1] < in.n ? in.g_start[g + 1] : in.n;
+    for (uint64_t k = in.g_start[g]; k < hi; k++) {
+      if (in.l_auth[k] != a) continue;
+      const uint32_t at = atomicAdd(st.cand_n + k, 1u);
+      if (at < DG_CAND) st.cand_slot[DG_CAND * k + at] = d.slot[rec];
+    }
   }
-}
+};
 
 // which (record of a list, row) a wave works on; false: none
 __device__ inline bool wave_task(const DagStore& d, uint64_t nb, const DecideIn& in, const uint32_t* __restrict__ list,
@@ -253,7 +239,7 @@ __global__ void __launch_bounds__(WG) k_dg_decide(const u64* __restrict__ slots,
 //                 not SKIP -- not final yet: wait for a later pass; COMMIT: the anchor, whose walk job
 //                 is claimed once and takes the lowest target round; anything else: blocked
 //   k_cm_seed     a lane per job: the anchor's record into the job's marks
-//   k_cm_span_*   once per call: the records of the rounds a level can read, count / scan / list
+//   SpanList      once per call: the records of the rounds a level can read, a compaction pass
 //   k_cm_reach    one launch per level q some job passes, a wave per record of the span, at work when
 //                 its round is q + 1: for every job whose walk passes the level and that marks
 //                 it, the includes of key round q in batches of 64 -- with a record: marked; without: the
@@ -355,25 +341,17 @@ __global__ void __launch_bounds__(WG) k_cm_seed(DagStore d, uint64_t nb, uint64_
   wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
 }
 
-// the records of rounds lo..hi, the only ones a level of the call can read: count / scan / list
-__device__ inline bool in_span(const DagStore& d, uint64_t nb, uint64_t rec, uint64_t lo, uint64_t hi) {
-  return rec < nb && d.round[rec] >= lo && d.round[rec] <= hi;
-}
-__global__ void __launch_bounds__(WG) k_cm_span_count(DagStore d, uint64_t nb, uint64_t lo, uint64_t hi,
-                                                      uint64_t* __restrict__ wgcount) {
-  const uint64_t rec = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  (void)wg_excl(in_span(d, nb, rec, lo, hi), &tot);
-  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(WG) k_cm_span_list(DagStore d, uint64_t nb, uint64_t lo, uint64_t hi,
-                                                     const uint64_t* __restrict__ wgbase, uint32_t* __restrict__ span) {
-  const uint64_t rec = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  const bool in = in_span(d, nb, rec, lo, hi);
-  uint64_t tot;
-  const uint64_t at = wgbase[blockIdx.x] + wg_excl(in, &tot);
-  if (in && at < nb) span[at] = (uint32_t)rec;
-}
+// the records of rounds lo..hi, the only ones a level of the call can read, in record order
+struct SpanList {
+  static constexpr int WEIGHTS = 1;
+  DagStore d;
+  uint64_t nb, lo, hi;
+  uint32_t* span;
+  __device__ void weigh(uint64_t rec, uint64_t* in) const { *in = rec < nb && d.round[rec] >= lo && d.round[rec] <= hi; }
+  __device__ void place(uint64_t rec, uint64_t in, uint64_t at) const {
+    if (in && at < nb) span[at] = (uint32_t)rec;
+  }
+};
 
 __global__ void __launch_bounds__(WG) k_cm_reach(const u64* __restrict__ slots, DagStore d, uint64_t nb, DecideIn in,
                                                  CommitState cs, uint64_t njobs, uint64_t nspan, uint64_t q,
@@ -544,13 +522,7 @@ using namespace mv::ix;
 hipError_t launch_decide_pick(const DagStore& d, uint64_t nb, const DecideIn& in, const DecideState& st, uint64_t* wg,
                               uint64_t* ctl, hipStream_t s) {
   if (nb == 0) return hipSuccess;
-  const uint64_t nwg = index_groups(nb);
-  const WgScan w = wg_scan_of(wg, nb);
-  const dim3 g(grid_of(nb)), b(WG);
-  hipLaunchKernelGGL(k_dg_pick_count, g, b, 0, s, d, nb, in, w.count_a, w.count_b);
-  (void)launch_index_scan(w.count_a, nwg, w.base_a, ctl + IX_CTL_DG_NVOTE, nullptr, s);
-  (void)launch_index_scan(w.count_b, nwg, w.base_b, ctl + IX_CTL_DG_NDEC, nullptr, s);
-  hipLaunchKernelGGL(k_dg_pick_list, g, b, 0, s, d, nb, in, st, w.base_a, w.base_b);
+  compact_pass(PickRoles{d, nb, in, st}, nb, wg_scan_of(wg, nb), ctl + IX_CTL_DG_NVOTE, ctl + IX_CTL_DG_NDEC, nullptr, s);
   return hipGetLastError();
 }
 
@@ -589,11 +561,7 @@ hipError_t launch_commit_chain(const DecideIn& in, const CommitState& cs, const 
 hipError_t launch_commit_span(const DagStore& d, uint64_t nb, uint64_t lo, uint64_t hi, uint32_t* span, uint64_t* wg,
                               uint64_t* ctl, hipStream_t s) {
   if (nb == 0) return hipSuccess;
-  const WgScan w = wg_scan_of(wg, nb);
-  const dim3 g(grid_of(nb)), b(WG);
-  hipLaunchKernelGGL(k_cm_span_count, g, b, 0, s, d, nb, lo, hi, w.count_a);
-  (void)launch_index_scan(w.count_a, index_groups(nb), w.base_a, ctl + IX_CTL_CM_NSPAN, nullptr, s);
-  hipLaunchKernelGGL(k_cm_span_list, g, b, 0, s, d, nb, lo, hi, w.base_a, span);
+  compact_pass(SpanList{d, nb, lo, hi, span}, nb, wg_scan_of(wg, nb), ctl + IX_CTL_CM_NSPAN, nullptr, nullptr, s);
   return hipGetLastError();
 }
 

@@ -12,7 +12,7 @@ namespace {
 constexpr uint64_t kMaxDecideWaves = 1ull << 26;
 
 // One decide call on stream s (include/mysti_verify.h, mv_decide_leaders): the rows sorted by round
-// on the host, k_dg_pick, the counts of voting and decision records read back (they size the
+// on the host, the PickRoles pass, the counts of voting and decision records read back (they size the
 // next launches), k_dg_vote, k_dg_cert, k_dg_decide. Results go to d_out / d_stakes (device).
 // A commit call passes `keep`: k_dg_cert then also leaves its certificate masks, and the call's
 // arrays are handed on; without it the launches are those of a decide call, one for one.

@@ -51,15 +51,15 @@ mv_status index_resize(mv_ctx* ctx, Device& dev, uint64_t slots, hipStream_t s) 
     const Pending& pd = ix.pend;
     if (pd.nb) {
       const mvk::PendStore p = pend_view(pd, pd.cur);
-      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, p.slot, pd.nb, ix.ctl.as<uint64_t>(), s));
-      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, p.inc, pd.ni, ix.ctl.as<uint64_t>(), s));
+      HIPCHK(ctx, mvk::launch_index_reresolve(ix.tab.as<uint64_t>(), old_slots, nt, p.slot, pd.nb, ix.ctl.as<uint64_t>(), s));
+      HIPCHK(ctx, mvk::launch_index_reresolve(ix.tab.as<uint64_t>(), old_slots, nt, p.inc, pd.ni, ix.ctl.as<uint64_t>(), s));
     }
     // ... and so does the DAG store
     const Dag& dg = ix.dag;
     if (dg.on && dg.nb) {
       const mvk::DagStore d = dag_view(dg);
-      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, d.slot, dg.nb, ix.ctl.as<uint64_t>(), s));
-      HIPCHK(ctx, mvk::launch_pend_reresolve(ix.tab.as<uint64_t>(), nt, d.inc, dg.ni, ix.ctl.as<uint64_t>(), s));
+      HIPCHK(ctx, mvk::launch_index_reresolve(ix.tab.as<uint64_t>(), old_slots, nt, d.slot, dg.nb, ix.ctl.as<uint64_t>(), s));
+      HIPCHK(ctx, mvk::launch_index_reresolve(ix.tab.as<uint64_t>(), old_slots, nt, d.inc, dg.ni, ix.ctl.as<uint64_t>(), s));
     }
     // ... and the proposer's state
     if (ix.prop.on) {

@@ -160,11 +160,11 @@ mv_status mvi::propose_follow_table(mv_ctx* ctx, Device& dev, uint64_t old_slots
   Propose& pp = ix.prop;
   const uint64_t* old = ix.tab.as<uint64_t>();
   uint64_t* ctl = ix.ctl.as<uint64_t>();
-  if (pp.qn) HIPCHK(ctx, mvk::launch_propose_reresolve(old, old_slots, nt, queue_view(pp, pp.cur).slot, pp.qn, ctl, s));
+  if (pp.qn) HIPCHK(ctx, mvk::launch_index_reresolve(old, old_slots, nt, queue_view(pp, pp.cur).slot, pp.qn, ctl, s));
   if (pp.has_own)
-    HIPCHK(ctx, mvk::launch_propose_reresolve(old, old_slots, nt, pp.own[pp.own_cur].as<uint64_t>(), 1 + pp.own_k, ctl, s));
+    HIPCHK(ctx, mvk::launch_index_reresolve(old, old_slots, nt, pp.own[pp.own_cur].as<uint64_t>(), 1 + pp.own_k, ctl, s));
   if (pp.outstanding && pp.n_choice)
-    HIPCHK(ctx, mvk::launch_propose_reresolve(old, old_slots, nt, pp.choice.as<uint64_t>(), pp.n_choice, ctl, s));
+    HIPCHK(ctx, mvk::launch_index_reresolve(old, old_slots, nt, pp.choice.as<uint64_t>(), pp.n_choice, ctl, s));
   pp.stamp_slots = 0;  // the stamps are per slot of the table: remade and zeroed by the next take
   return MV_OK;
 }

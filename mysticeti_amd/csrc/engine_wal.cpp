@@ -192,13 +192,13 @@ mv_status replay_run(mv_ctx* ctx, Device& dev, const uint8_t* d_img, uint64_t si
   if (n) {
     // per workgroup: count | base; per entry (the lists' bound): off | len | ent | block status
     const size_t nwg = mvk::replay_groups(n), a64 = rp_al(8 * n);
-    const size_t o_base = rp_al(4 * nwg), o_list = o_base + rp_al(8 * nwg);
+    const size_t o_base = rp_al(8 * nwg), o_list = o_base + rp_al(8 * nwg);
     HIPCHK(ctx, dev.wal.rscr.ensure(o_list + 3 * a64 + rp_al(n)));
     char* b = dev.wal.rscr.as<char>();
     uint64_t* wgbase = (uint64_t*)(b + o_base);
     bl = mvk::ReplayBlocks{(uint64_t*)(b + o_list), (uint64_t*)(b + o_list + a64), (uint64_t*)(b + o_list + 2 * a64),
                            (uint8_t*)(b + o_list + 3 * a64), 0, n};
-    HIPCHK(ctx, mvk::launch_replay_select(en, size, (uint32_t*)b, wgbase, ctl + mvk::REPLAY_CTL_NB, s));
+    HIPCHK(ctx, mvk::launch_replay_select(en, size, (uint64_t*)b, wgbase, ctl + mvk::REPLAY_CTL_NB, s));
     uint64_t nb = 0;
     HIPCHK(ctx, hipMemcpyAsync(&nb, ctl + mvk::REPLAY_CTL_NB, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));

@@ -11,7 +11,7 @@
 
 namespace mv::ix {
 
-// wgbase[g] = the counts of the workgroups before g; *total = all of them (k_replay_scan's shape).
+// wgbase[g] = the counts of the workgroups before g; *total = all of them.
 // With `running` (the connect sweep's rows so far): the bases stand behind *running; *running += *total
 __global__ void __launch_bounds__(1024) k_ix_scan(const uint64_t* __restrict__ wgcount, uint64_t nwg,
                                                   uint64_t* __restrict__ wgbase, uint64_t* __restrict__ total,
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(WG) k_ix_claim(IndexTable t, IndexKeys ks, uin
       }
       break;
     }
-    probe = (uint32_t)(dist < 0xffffffffull ? dist + 1 : 0xffffffffull);
+    probe = probe_len(dist);
     fail = code_of(res) == C_FAIL;
     item[i] = res;
   }
@@ -197,50 +197,57 @@ __global__ void __launch_bounds__(WG) k_ix_rebuild(const u64* __restrict__ old, 
     const u64* src = old + SLOT_WORDS * i;
     const uint32_t st = (uint32_t)src[1];
     if (src[0] != 0 && st != 0) {
-      uint64_t k[6], start, tag;
+      uint64_t k[6];
 #pragma unroll
       for (int w = 0; w < 6; w++) k[w] = src[2 + w];
-      hash_key(t, k, &start, &tag);
-      uint64_t p = start, dist = 0;
-      fail = true;
-      for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
-        u64* slot = t.slots + SLOT_WORDS * p;
-        if (atomicCAS(slot, 0ull, (u64)tag) != 0) continue;
-#pragma unroll
-        for (int w = 0; w < 6; w++) slot[2 + w] = k[w];
-        slot[1] = st;
-        fail = false;
-        break;
-      }
-      probe = (uint32_t)(dist < 0xffffffffull ? dist + 1 : 0xffffffffull);
+      fail = claim_fresh(t, k, st, &probe) == DG_NO_SLOT;
     }
   }
   wave_max_to(ctl + mvk::IX_CTL_MAXPROBE, probe);
   wave_count_to(ctl + mvk::IX_CTL_ERR, fail);
 }
 
-// The WANTED entries, listed by count / scan / list over the slots
-__device__ inline bool slot_wanted(const u64* slots, uint64_t i, uint64_t n) {
-  return i < n && slots[SLOT_WORDS * i] != 0 && (uint32_t)slots[SLOT_WORDS * i + 1] == MV_REF_WANTED;
-}
-__global__ void __launch_bounds__(WG) k_ix_wanted_count(const u64* __restrict__ slots, uint64_t n,
-                                                        uint64_t* __restrict__ wgcount) {
+// After k_ix_rebuild: the slot numbers a store holds (records, includes, queue entries) become
+// those of the same keys in the new table, by read-only probes of a table that an earlier launch
+// filled. DG_NO_SLOT stays; a number outside the old table, or a key without an entry, becomes
+// DG_NO_SLOT and counts into the error word. The probe length is reported, though it tells nothing
+// new: a key is found at exactly the slot where k_ix_rebuild placed it, and k_ix_rebuild reported
+// that probe length on the same stream.
+__global__ void __launch_bounds__(WG) k_ix_reresolve(const u64* __restrict__ old, uint64_t n_old, IndexTable t,
+                                                     uint64_t* __restrict__ slotidx, uint64_t n, u64* __restrict__ ctl) {
   const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  (void)wg_excl(slot_wanted(slots, i, n), &tot);
-  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(WG) k_ix_wanted_list(const u64* __restrict__ slots, uint64_t n,
-                                                       const uint64_t* __restrict__ wgbase, uint64_t* __restrict__ out,
-                                                       uint64_t cap) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  const bool w = slot_wanted(slots, i, n);
-  uint64_t tot;
-  const uint64_t r = wgbase[blockIdx.x] + wg_excl(w, &tot);
-  if (!w || r >= cap) return;
+  uint32_t probe = 0;
+  bool bad = false;
+  if (i < n && slotidx[i] != DG_NO_SLOT) {
+    const uint64_t o = slotidx[i];
+    u64 s = DG_NO_SLOT;
+    if (o < n_old) {
+      uint64_t k[6];
 #pragma unroll
-  for (int k = 0; k < 6; k++) out[6 * r + k] = slots[SLOT_WORDS * i + 2 + k];
+      for (int w = 0; w < 6; w++) k[w] = old[SLOT_WORDS * o + 2 + w];
+      s = find_slot(t, k, &probe, &bad);
+    }
+    bad = s == DG_NO_SLOT;
+    slotidx[i] = s;
+  }
+  wave_max_to(ctl + mvk::IX_CTL_MAXPROBE, probe);
+  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
 }
+
+// The WANTED entries, listed in slot order
+struct WantedList {
+  static constexpr int WEIGHTS = 1;
+  const u64* slots;
+  uint64_t n;
+  uint64_t* out;
+  uint64_t cap;
+  __device__ void weigh(uint64_t i, uint64_t* w) const {
+    *w = i < n && slots[SLOT_WORDS * i] != 0 && (uint32_t)slots[SLOT_WORDS * i + 1] == MV_REF_WANTED;
+  }
+  __device__ void place(uint64_t i, uint64_t w, uint64_t r) const {
+    if (w && r < cap) copy_key(out + 6 * r, slots + SLOT_WORDS * i);
+  }
+};
 
 // ---------------------------------------------------------------- the accept call
 
@@ -289,12 +296,12 @@ __global__ void __launch_bounds__(WG) k_acc_vlist(AcceptArrays a) {
 __device__ inline bool group_head(const AcceptArrays& a, uint64_t i) {
   return i < a.n && (i == 0 || a.grp[i] != a.grp[i - 1]);
 }
-__global__ void __launch_bounds__(WG) k_acc_heads(AcceptArrays a) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  (void)wg_excl(group_head(a, i), &tot);
-  if (threadIdx.x == 0) a.wg_a[blockIdx.x] = tot;
-}
+// the heads per workgroup (count and scan only: k_acc_groups ranks for itself, a head counts itself in)
+struct GroupHeads {
+  static constexpr int WEIGHTS = 1;
+  AcceptArrays a;
+  __device__ void weigh(uint64_t i, uint64_t* w) const { *w = group_head(a, i); }
+};
 
 // statuses (KNOWN blocks are MV_BLOCK_OK unverified), the group of every block, and a reject flag
 // per group: one rejected block drops its message before add_blocks (net_sync.rs:352-361)
@@ -372,38 +379,25 @@ __global__ void __launch_bounds__(WG) k_acc_inc_src(AcceptArrays a, uint64_t nca
                                                     uint64_t* __restrict__ inc_src) {
   const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
   if (j >= ninc) return;
-  uint64_t lo = 0, hi = ncand;  // the last candidate whose first include is <= j
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (a.inc_base[mid] <= j) lo = mid;
-    else hi = mid;
-  }
+  const uint64_t lo = cand_of_include(a.inc_base, ncand, j);
   const uint64_t q = j - a.inc_base[lo];
   const bool is_new = a.state[a.cand_blk[lo]] == MV_ACC_NEW && q < a.kc[a.cand_blk[lo]];
   inc_src[j] = is_new ? a.cand_src[lo] + br::include_off(q) : mvk::IX_NO_SRC;
 }
 
 // the includes that created an entry are the missing references, in (block, include) order
-__device__ inline bool item_created(const u64* item, uint64_t j, uint64_t n) { return j < n && code_of(item[j]) == C_NEW; }
-__global__ void __launch_bounds__(WG) k_acc_miss_count(const u64* __restrict__ item, uint64_t n,
-                                                       uint64_t* __restrict__ wgcount) {
-  const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  (void)wg_excl(item_created(item, j, n), &tot);
-  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(WG) k_acc_miss_list(IndexTable t, const u64* __restrict__ item, uint64_t n,
-                                                      const uint64_t* __restrict__ wgbase, uint64_t* __restrict__ out,
-                                                      uint64_t cap) {
-  const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  const bool m = item_created(item, j, n);
-  uint64_t tot;
-  const uint64_t r = wgbase[blockIdx.x] + wg_excl(m, &tot);
-  if (!m || r >= cap) return;
-  const u64* slot = t.slots + SLOT_WORDS * (item[j] & SLOT_MASK);
-#pragma unroll
-  for (int k = 0; k < 6; k++) out[6 * r + k] = slot[2 + k];
-}
+struct MissingList {
+  static constexpr int WEIGHTS = 1;
+  IndexTable t;
+  const u64* item;
+  uint64_t n;
+  uint64_t* out;
+  uint64_t cap;
+  __device__ void weigh(uint64_t j, uint64_t* w) const { *w = j < n && code_of(item[j]) == C_NEW; }
+  __device__ void place(uint64_t j, uint64_t w, uint64_t r) const {
+    if (w && r < cap) copy_key(out + 6 * r, t.slots + SLOT_WORDS * (item[j] & SLOT_MASK));
+  }
+};
 
 }  // namespace mv::ix
 
@@ -452,14 +446,17 @@ hipError_t launch_index_rebuild(const uint64_t* old_slots, uint64_t n_old, const
   return hipGetLastError();
 }
 
+hipError_t launch_index_reresolve(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* slotidx,
+                                  uint64_t n, uint64_t* ctl, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ix_reresolve, dim3(grid_of(n)), dim3(WG), 0, s, (const u64*)old_slots, n_old, t, slotidx, n, (u64*)ctl);
+  return hipGetLastError();
+}
+
 hipError_t launch_index_wanted(const IndexTable& t, uint64_t* wg, uint64_t* total, uint64_t* out, uint64_t cap,
                                hipStream_t s) {
   const uint64_t n = t.mask + 1;
-  const WgScan w = wg_scan_of(wg, n);
-  const dim3 g(grid_of(n)), b(WG);
-  hipLaunchKernelGGL(k_ix_wanted_count, g, b, 0, s, (const u64*)t.slots, n, w.count_a);
-  (void)launch_index_scan(w.count_a, index_groups(n), w.base_a, total, nullptr, s);
-  if (cap) hipLaunchKernelGGL(k_ix_wanted_list, g, b, 0, s, (const u64*)t.slots, n, w.base_a, out, cap);
+  compact_pass(WantedList{(const u64*)t.slots, n, out, cap}, n, wg_scan_of(wg, n), total, nullptr, nullptr, s, cap != 0);
   return hipGetLastError();
 }
 
@@ -474,10 +471,7 @@ hipError_t launch_accept_probe(const IndexTable& t, const AcceptArrays& a, uint6
 hipError_t launch_accept_groups(const AcceptArrays& a, uint64_t* ctl, hipStream_t s) {
   const dim3 g(grid_of(a.n)), b(WG);
   const uint64_t nwg = index_groups(a.n);
-  if (a.grp) {
-    hipLaunchKernelGGL(k_acc_heads, g, b, 0, s, a);
-    (void)launch_index_scan(a.wg_a, nwg, a.base_a, ctl + IX_CTL_NHEADS, nullptr, s);
-  }
+  if (a.grp) compact_count(GroupHeads{a}, a.n, WgScan{a.wg_a, a.wg_b, a.base_a, a.base_b}, ctl + IX_CTL_NHEADS, nullptr, nullptr, s);
   hipLaunchKernelGGL(k_acc_groups, g, b, 0, s, a);
   hipLaunchKernelGGL(k_acc_states, g, b, 0, s, a);
   (void)launch_index_scan(a.wg_a, nwg, a.base_a, ctl + IX_CTL_NCAND, nullptr, s);
@@ -501,11 +495,8 @@ hipError_t launch_accept_inc_src(const AcceptArrays& a, uint64_t ncand, uint64_t
 hipError_t launch_accept_missing(const IndexTable& t, const uint64_t* item, uint64_t ninc, uint64_t* wg, uint64_t* ctl,
                                  uint64_t* out, uint64_t cap, hipStream_t s) {
   if (ninc == 0) return hipSuccess;
-  const WgScan w = wg_scan_of(wg, ninc);
-  const dim3 g(grid_of(ninc)), b(WG);
-  hipLaunchKernelGGL(k_acc_miss_count, g, b, 0, s, (const u64*)item, ninc, w.count_a);
-  (void)launch_index_scan(w.count_a, index_groups(ninc), w.base_a, ctl + IX_CTL_NMISS, nullptr, s);
-  if (cap) hipLaunchKernelGGL(k_acc_miss_list, g, b, 0, s, t, (const u64*)item, ninc, w.base_a, out, cap);
+  compact_pass(MissingList{t, (const u64*)item, ninc, out, cap}, ninc, wg_scan_of(wg, ninc), ctl + IX_CTL_NMISS, nullptr,
+               nullptr, s, cap != 0);
   return hipGetLastError();
 }
 

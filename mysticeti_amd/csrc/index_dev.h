@@ -1,6 +1,8 @@
-// What the index kernels share (index.hip, pending.hip, dag_store.hip, decide.hip): the table's slot
-// layout, the item record of an insert, the keyed hash, the read-only probe and the wave and
-// workgroup reductions. The build has no relocatable device code: everything here is inline.
+// What the index kernels share (index.hip, pending.hip, dag_store.hip, decide.hip, linearize.hip,
+// propose.hip, votes.hip; replay.hip for the workgroup prefix): the table's slot layout, the item
+// record of an insert, the keyed hash, the read-only probe, the claim into a fresh table, the wave
+// and workgroup reductions and the compaction pass. The build has no relocatable device code:
+// everything here is inline or a template.
 //
 // Table: open addressing, linear probing, 64-byte slots of eight u64 words
 //   [0] tag    0 = empty, else the (truncated) second hash of the key, never 0
@@ -28,6 +30,17 @@
 // all the time). All items with one key stop at the same slot in a round (tags are set once and
 // never cleared), so they share their fate, and the owner among them is the lowest item.
 // Every probe loop is bounded by the table size; a probe that runs out sets the error word.
+//
+// Compaction. A stable "count per workgroup, k_ix_scan, list at the scanned place" pass is one
+// functor F through compact_pass (k_compact_count<F>, launch_index_scan, k_compact_list<F>):
+//   F::WEIGHTS            1 or 2: a one-weight pass does one wg_excl per kernel and one scan launch
+//   weigh(i, &a[, &b])    the item's weights -- 0 / 1 for a flag, or a count such as its includes
+//   place(i, a, ra[, b, rb])  the item's weights again and their exclusive ranks over all items
+// Every lane of every workgroup calls both, the lanes with i >= n included (their weights are 0):
+// the workgroup prefix has barriers, and place() is where a pass does its all-lane extras such as
+// wave_count_to. The predicate is stated once, in weigh(); the list kernel hands place() what it
+// gave. Items keep their order: the rank of item i is the sum of the weights of the items below i.
+// Caps and bounds checks are place()'s own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -130,6 +143,14 @@ __device__ inline bool key_eq(const u64* slot, const uint64_t k[6]) {
   for (int w = 0; w < 6; w++) eq &= slot[2 + w] == k[w];
   return eq;
 }
+// the six key words of a slot to dst: all loads ahead of the stores (the two may alias for all the compiler knows)
+__device__ inline void copy_key(uint64_t* dst, const u64* slot) {
+  u64 k[6];
+#pragma unroll
+  for (int w = 0; w < 6; w++) k[w] = slot[2 + w];
+#pragma unroll
+  for (int w = 0; w < 6; w++) dst[w] = k[w];
+}
 __device__ inline uint32_t* meta_of(u64* slot) { return reinterpret_cast<uint32_t*>(slot + 1); }
 __device__ inline uint32_t slot_state(const u64* slots, uint64_t p) { return (uint32_t)slots[SLOT_WORDS * p + 1]; }
 __device__ inline bool item_has_slot(u64 it) {
@@ -137,13 +158,19 @@ __device__ inline bool item_has_slot(u64 it) {
   return c == C_NEW || c == C_RAISED || c == C_DUP || c == C_NOOP;
 }
 
-// Read-only probe: the state of key k, MV_REF_ABSENT without an entry. Nothing writes the table
-// in a launch that calls it. *probe = slots examined.
-__device__ inline uint32_t lookup(const IndexTable& t, const uint64_t k[6], uint32_t* probe, bool* fail) {
+constexpr u64 DG_NO_SLOT = mvk::DG_NO_SLOT;
+__device__ inline uint32_t probe_len(uint64_t dist) { return (uint32_t)(dist < 0xffffffffull ? dist + 1 : 0xffffffffull); }
+
+// Read-only probe: the slot of key k, DG_NO_SLOT without an entry (no table yet, an empty slot met
+// first, or -- *fail -- the probe ran through the whole table). Nothing writes the table in a launch
+// that calls it. *probe = slots examined, for the callers that report IX_CTL_MAXPROBE.
+__device__ inline u64 find_slot(const IndexTable& t, const uint64_t k[6], uint32_t* probe, bool* fail) {
+  *probe = 0, *fail = false;
+  if (!t.slots) return DG_NO_SLOT;
   uint64_t start, tag;
   hash_key(t, k, &start, &tag);
   uint64_t p = start, dist = 0;
-  uint32_t st = MV_REF_ABSENT;
+  u64 at = DG_NO_SLOT;
   bool ended = false;
   for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
     const u64* slot = t.slots + SLOT_WORDS * p;
@@ -153,14 +180,40 @@ __device__ inline uint32_t lookup(const IndexTable& t, const uint64_t k[6], uint
       break;
     }
     if (g == tag && key_eq(slot, k)) {
-      st = (uint32_t)slot[1];
+      at = p;
       ended = true;
       break;
     }
   }
-  *probe = (uint32_t)(dist < 0xffffffffull ? dist + 1 : 0xffffffffull);
+  *probe = probe_len(dist);
   *fail = !ended;
-  return st;
+  return at;
+}
+// the state of key k, MV_REF_ABSENT without an entry
+__device__ inline uint32_t lookup(const IndexTable& t, const uint64_t k[6], uint32_t* probe, bool* fail) {
+  const u64 p = find_slot(t, k, probe, fail);
+  return p == DG_NO_SLOT ? (uint32_t)MV_REF_ABSENT : slot_state(t.slots, p);
+}
+
+// An entry into a fresh table whose keys are distinct (a rebuild, a move): the first empty slot is
+// claimed by CAS, its key and meta word written, and nothing compares (no key of this launch is
+// read). The slot, or DG_NO_SLOT when the probe ran through the whole table; *probe = slots examined.
+__device__ inline u64 claim_fresh(const IndexTable& t, const uint64_t k[6], u64 meta, uint32_t* probe) {
+  uint64_t start, tag;
+  hash_key(t, k, &start, &tag);
+  uint64_t p = start, dist = 0;
+  u64 at = DG_NO_SLOT;
+  for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
+    u64* slot = t.slots + SLOT_WORDS * p;
+    if (atomicCAS(slot, 0ull, (u64)tag) != 0) continue;
+#pragma unroll
+    for (int w = 0; w < 6; w++) slot[2 + w] = k[w];
+    slot[1] = meta;
+    at = p;
+    break;
+  }
+  *probe = probe_len(dist);
+  return at;
 }
 
 // the wave's maximum of v into *dst (every lane of the wave calls)
@@ -202,7 +255,6 @@ __device__ inline uint64_t wg_excl(uint64_t v, uint64_t* total) {
 }
 
 constexpr uint32_t DG_NONE = mvk::DG_NONE;
-constexpr u64 DG_NO_SLOT = mvk::DG_NO_SLOT;
 constexpr uint32_t DG_MAX_AUTH = mvk::DG_MAX_AUTH;
 constexpr int DG_BM = mvk::DG_BM_WORDS;
 constexpr uint32_t DG_CAND = MV_DECIDE_MAX_LEADER_BLOCKS;
@@ -236,6 +288,63 @@ __device__ inline uint64_t bitmap_stake(P bm, const uint64_t* __restrict__ stake
   return wave_sum64(stake);
 }
 
+// the last of the n candidates whose first include (inc_base[], ascending from 0) is <= j
+__device__ inline uint64_t cand_of_include(const uint64_t* __restrict__ inc_base, uint64_t n, uint64_t j) {
+  uint64_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (inc_base[mid] <= j) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
 static inline uint32_t grid_of(uint64_t items) { return (uint32_t)((items + WG - 1) / WG); }
+
+// ---------------------------------------------------------------- the compaction pass (contract: above)
+template <class F>
+__global__ void __launch_bounds__(WG) k_compact_count(const F f, const mvk::WgScan w) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t a = 0, b = 0, tot;
+  if constexpr (F::WEIGHTS == 2) f.weigh(i, &a, &b);
+  else f.weigh(i, &a);
+  (void)wg_excl(a, &tot);
+  if (threadIdx.x == 0) w.count_a[blockIdx.x] = tot;
+  if constexpr (F::WEIGHTS == 2) {
+    (void)wg_excl(b, &tot);
+    if (threadIdx.x == 0) w.count_b[blockIdx.x] = tot;
+  }
+}
+template <class F>
+__global__ void __launch_bounds__(WG) k_compact_list(const F f, const mvk::WgScan w) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  uint64_t a = 0, b = 0, tot;
+  if constexpr (F::WEIGHTS == 2) f.weigh(i, &a, &b);
+  else f.weigh(i, &a);
+  const uint64_t ra = w.base_a[blockIdx.x] + wg_excl(a, &tot);
+  if constexpr (F::WEIGHTS == 2) {
+    const uint64_t rb = w.base_b[blockIdx.x] + wg_excl(b, &tot);
+    f.place(i, a, ra, b, rb);
+  } else {
+    f.place(i, a, ra);
+  }
+}
+// count and scan(s) over n items (n > 0): *total_a (and *total_b) = the weights' sums; with `running`
+// (may be null) the first weight's ranks stand behind *running, which grows by its total
+template <class F>
+static inline void compact_count(const F& f, uint64_t n, const mvk::WgScan& w, uint64_t* total_a, uint64_t* total_b,
+                                 uint64_t* running, hipStream_t s) {
+  const uint64_t nwg = mvk::index_groups(n);
+  hipLaunchKernelGGL(k_compact_count<F>, dim3(grid_of(n)), dim3(WG), 0, s, f, w);
+  (void)mvk::launch_index_scan(w.count_a, nwg, w.base_a, total_a, running, s);
+  if constexpr (F::WEIGHTS == 2) (void)mvk::launch_index_scan(w.count_b, nwg, w.base_b, total_b, nullptr, s);
+}
+// count, scan(s), list; list = false (a cap of 0) only counts
+template <class F>
+static inline void compact_pass(const F& f, uint64_t n, const mvk::WgScan& w, uint64_t* total_a, uint64_t* total_b,
+                                uint64_t* running, hipStream_t s, bool list = true) {
+  compact_count(f, n, w, total_a, total_b, running, s);
+  if (list) hipLaunchKernelGGL(k_compact_list<F>, dim3(grid_of(n)), dim3(WG), 0, s, f, w);
+}
 
 }  // namespace mv::ix

@@ -369,9 +369,9 @@ struct ReplayBlocks {  // the entries that carry a block, in iteration order (li
 // kept, three maxima (highest round, last own row + 1, last state entry + 1); the rest preset to 0
 constexpr int REPLAY_CTL_NB = 0, REPLAY_CTL_FF = 1, REPLAY_CTL_NROWS = 2, REPLAY_CTL_ACC = 3, REPLAY_CTL_WORDS = 6;
 uint64_t replay_groups(uint64_t n);  // workgroups of the per-entry kernels: wgcount / wgbase hold one word each
-// k_replay_select + k_replay_scan: statuses of unknown tags and short own-block payloads, the
+// k_replay_select + launch_index_scan: statuses of unknown tags and short own-block payloads, the
 // per-workgroup block counts and their scan, *nb = the block total
-hipError_t launch_replay_select(const ReplayEntries& en, uint64_t size, uint32_t* wgcount, uint64_t* wgbase,
+hipError_t launch_replay_select(const ReplayEntries& en, uint64_t size, uint64_t* wgcount, uint64_t* wgbase,
                                 uint64_t* nb, hipStream_t s);
 hipError_t launch_replay_list(const ReplayEntries& en, uint64_t size, const uint64_t* wgbase, const ReplayBlocks& bl,
                               hipStream_t s);
@@ -494,6 +494,11 @@ hipError_t launch_index_lookup(const IndexTable& t, const IndexKeys& ks, uint64_
 // every entry of the old table into t (empty, zeroed)
 hipError_t launch_index_rebuild(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* ctl,
                                 hipStream_t s);
+// after launch_index_rebuild: the n slot numbers a store holds (some may be DG_NO_SLOT, which stays)
+// become those of the same keys in t; a number >= n_old or a key without an entry becomes DG_NO_SLOT
+// and counts into ctl[IX_CTL_ERR]
+hipError_t launch_index_reresolve(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* slotidx,
+                                  uint64_t n, uint64_t* ctl, hipStream_t s);
 // count / scan / list of the WANTED entries: *total, the first cap into out (cap x 6 words);
 // wg: wg_scan_bytes(slots), as for every launcher below that takes one (of its own item count)
 hipError_t launch_index_wanted(const IndexTable& t, uint64_t* wg, uint64_t* total, uint64_t* out, uint64_t cap,
@@ -532,7 +537,7 @@ hipError_t launch_accept_missing(const IndexTable& t, const uint64_t* item, uint
 // The suspended-block store (mv_connect_blocks; layout and sweep: pending.hip): one record per block
 // whose includes are not all MV_REF_STORED, in arrival order. The engine keeps two copies and
 // compacts from one into the other. References are held as slots of the table: a rebuild
-// re-resolves them (launch_pend_reresolve).
+// re-resolves them (launch_index_reresolve).
 struct PendStore {
   uint64_t* slot;   // per block: the slot of its own reference
   uint64_t* ibase;  // the number of its first include in inc
@@ -558,9 +563,6 @@ hipError_t launch_pend_level(const IndexTable& t, const PendStore& p, uint64_t n
 // MV_ACC_SUSPENDED in state (n_state entries, may be null). ctl[IX_CTL_PB_NB], ctl[IX_CTL_PB_NI] = what q holds.
 hipError_t launch_pend_compact(const IndexTable& t, const PendStore& p, const PendStore& q, uint64_t nb, uint64_t* newbase,
                                uint8_t* state, uint64_t n_state, uint64_t* wg, uint64_t* ctl, hipStream_t s);
-// after launch_index_rebuild: n slot numbers of the old table become those of the same keys in t
-hipError_t launch_pend_reresolve(const uint64_t* old_slots, const IndexTable& t, uint64_t* slotidx, uint64_t n,
-                                 uint64_t* ctl, hipStream_t s);
 
 // The DAG store (mv_dag_reserve, mv_decide_leaders; kernels: dag_store.hip, decide.hip): one
 // record per block that mv_connect_blocks stored, in connected-row order, with its includes as
@@ -650,7 +652,7 @@ struct DecideState {  // zeroed by the caller except vpos / vlist / dlist / sup
   uint8_t* cmask;       // null for a decide call; a commit call: per (place in dlist, row of that round) the
                         // candidates the decision record certifies, bit c for candidate c (zeroed by the caller)
 };
-// k_dg_pick: vpos, vlist, dlist, the candidates; ctl[IX_CTL_DG_NVOTE], ctl[IX_CTL_DG_NDEC]
+// PickRoles (decide.hip): vpos, vlist, dlist, the candidates; ctl[IX_CTL_DG_NVOTE], ctl[IX_CTL_DG_NDEC]
 hipError_t launch_decide_pick(const DagStore& d, uint64_t nb, const DecideIn& in, const DecideState& st,
                               uint64_t* wg, uint64_t* ctl, hipStream_t s);
 // k_dg_vote, k_dg_cert, k_dg_decide: out (n x 8) and stakes_out (n x 3, may be null) in the caller's row order
@@ -838,9 +840,6 @@ hipError_t launch_propose_own(const uint64_t* item, const uint64_t* prev, bool h
 // the own block's record behind d's nb records and ni includes, unless its slot has one: pctl[PP_CTL_APPENDED]
 hipError_t launch_propose_record(const IndexTable& t, const DagStore& d, uint64_t nb, uint64_t ni, const uint64_t* own,
                                  uint64_t k, uint64_t* pctl, uint64_t* ctl, hipStream_t s);
-// after launch_index_rebuild: as launch_pend_reresolve, for n slot numbers of which some are DG_NO_SLOT
-hipError_t launch_propose_reresolve(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* slotidx,
-                                    uint64_t n, uint64_t* ctl, hipStream_t s);
 
 // seal.hip: mv_seal_blocks (StatementBlock::new_with_signer on bincode blocks with placeholder
 // digest and signature fields). keys: 24 words per authority (a mod l, prefix, public key).

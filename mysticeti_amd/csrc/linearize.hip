@@ -49,30 +49,14 @@ __device__ inline u64 key_word(uint32_t cidx, const u64* p, uint32_t j, int w) {
   return ((p[LN_PW - 1] & 0xffffull) << 48) | ((u64)j << 32);
 }
 
-// the slot of key k, DG_NO_SLOT without an entry (read-only probe, bounded by the table)
-__device__ inline u64 find_slot(const IndexTable& t, const uint64_t k[6], bool* fail) {
-  *fail = false;
-  if (!t.slots) return DG_NO_SLOT;
-  uint64_t start, tag;
-  hash_key(t, k, &start, &tag);
-  uint64_t p = start, dist = 0;
-  for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
-    const u64* slot = t.slots + SLOT_WORDS * p;
-    const u64 g = slot[0];
-    if (g == 0) return DG_NO_SLOT;
-    if (g == tag && key_eq(slot, k)) return p;
-  }
-  *fail = true;
-  return DG_NO_SLOT;
-}
-
 __global__ void __launch_bounds__(WG) k_ln_roots(IndexTable t, DagStore d, uint64_t nb, LinState ls, u64* __restrict__ ctl) {
   const uint64_t k = (uint64_t)blockIdx.x * WG + threadIdx.x;
   bool bad = false;
   if (k < ls.n) {
     uint64_t key[6];
     for (int w = 0; w < 6; w++) key[w] = ls.leaders[6 * k + w];
-    u64 s = find_slot(t, key, &bad);
+    uint32_t probe;  // (not reported: this call's probes never were)
+    u64 s = find_slot(t, key, &probe, &bad);
     uint32_t fail = 0;
     if (s >= d.n_slots) {
       fail = MV_LINEAR_INCOMPLETE;
@@ -387,7 +371,8 @@ __global__ void __launch_bounds__(WG) k_ln_carry(const u64* __restrict__ old, ui
   if (i < n_old && old_mark[i] && old[SLOT_WORDS * i] != 0) {
     uint64_t k[6];
     for (int w = 0; w < 6; w++) k[w] = old[SLOT_WORDS * i + 2 + w];
-    const u64 s = find_slot(t, k, &bad);
+    uint32_t probe;
+    const u64 s = find_slot(t, k, &probe, &bad);
     if (s > t.mask) bad = true;
     else atomicExch(mark + s, 1u);
   }

@@ -8,8 +8,8 @@
 // into the error word (MV_E_HIP) and is not followed. Every loop is bounded by a count read under such
 // a check.
 //   k_pp_resolve   a lane per row: its slot by a probe of the table, its round and authority
-//   k_pp_bit_*     one pass of the stable sort by round (a pass per bit in which the call's rounds
-//                  differ): zeros per workgroup, (scan,) scatter
+//   SortBit        one pass of the stable sort by round (a pass per bit in which the call's rounds
+//                  differ): a compaction pass of index_dev.h over the zeros, the ones behind them
 //   k_pp_append    a lane per sorted row: its queue entry; the payload entry behind them
 //   k_pp_seg       the clock, batch form: a wave per segment of equal round -- which rows are the first
 //                  of their author (an LDS table of first rows per authority), the prefix of their
@@ -19,33 +19,16 @@
 //                  words, one that continues a set is walked 64 rows a step with the set in LDS
 //   k_pp_cut       the first include entry at or above the clock round
 //   k_pp_stamp     a wave per taken entry (and one for the own last block): lanes over its record's includes
-//   k_pp_keep_*    count, (scan,) list: the stable compaction of the unstamped include entries, the payloads
+//   KeepEntries    a compaction pass: the unstamped include entries and the payloads, each in queue order
 //   k_pp_shift     the tail moves to the front (into the queue's other copy)
 //   k_pp_own, k_pp_record   the own last block's slots; its record in the DAG store
-//   k_pp_reresolve after a rebuild: slot numbers of the old table become those of the same keys
+// After a rebuild the queue's, the own block's and the choice's slot numbers go through index.hip's k_ix_reresolve.
 #include "index_dev.h"
 
 namespace mv::ix {
 
 using mvk::PropClock;
 using mvk::PropQueue;
-
-// the slot of key k, DG_NO_SLOT without an entry (read-only probe, bounded by the table)
-__device__ inline u64 pp_find(const IndexTable& t, const uint64_t k[6], bool* fail) {
-  *fail = false;
-  if (!t.slots) return DG_NO_SLOT;
-  uint64_t start, tag;
-  hash_key(t, k, &start, &tag);
-  uint64_t p = start, dist = 0;
-  for (; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
-    const u64* slot = t.slots + SLOT_WORDS * p;
-    const u64 g = slot[0];
-    if (g == 0) return DG_NO_SLOT;
-    if (g == tag && key_eq(slot, k)) return p;
-  }
-  *fail = true;
-  return DG_NO_SLOT;
-}
 
 __global__ void __launch_bounds__(WG) k_pp_resolve(IndexTable t, const uint64_t* __restrict__ rows, uint64_t n, uint64_t stride,
                                                    uint32_t n_auth, uint64_t* __restrict__ slot, uint64_t* __restrict__ round,
@@ -56,7 +39,8 @@ __global__ void __launch_bounds__(WG) k_pp_resolve(IndexTable t, const uint64_t*
   if (i < n) {
     uint64_t k[6];
     for (int w = 0; w < 6; w++) k[w] = rows[stride * i + w];
-    const u64 s = pp_find(t, k, &bad);
+    uint32_t probe;  // (not reported: this call's probes never were)
+    const u64 s = find_slot(t, k, &probe, &bad);
     // (StakeAggregator::add panics on an authority outside the committee, committee.rs:315)
     miss = s == DG_NO_SLOT || k[0] >= n_auth;
     slot[i] = s;
@@ -70,31 +54,25 @@ __global__ void __launch_bounds__(WG) k_pp_resolve(IndexTable t, const uint64_t*
   wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
 }
 
-__device__ inline bool sort_zero(const uint64_t* round, int bit, const uint32_t* perm, uint64_t n, uint64_t i) {
-  if (i >= n) return false;
-  const uint32_t r = perm[i];
-  return r < n && ((round[r] >> bit) & 1) == 0;
-}
-__global__ void __launch_bounds__(WG) k_pp_bit_count(const uint64_t* __restrict__ round, int bit,
-                                                     const uint32_t* __restrict__ perm, uint64_t n, uint64_t* __restrict__ wgcount) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  (void)wg_excl(sort_zero(round, bit, perm, n, i), &tot);
-  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(WG) k_pp_bit_scatter(const uint64_t* __restrict__ round, int bit,
-                                                       const uint32_t* __restrict__ perm, uint32_t* __restrict__ out, uint64_t n,
-                                                       const uint64_t* __restrict__ wgbase, const u64* __restrict__ pctl) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  const bool z = sort_zero(round, bit, perm, n, i);
-  uint64_t tot;
-  const uint64_t zb = wgbase[blockIdx.x] + wg_excl(z, &tot);  // the zeros before i
-  if (i < n) {
+struct SortBit {
+  static constexpr int WEIGHTS = 1;
+  const uint64_t* round;
+  int bit;
+  const uint32_t* perm;
+  uint32_t* out;
+  uint64_t n;
+  const u64* pctl;
+  __device__ void weigh(uint64_t i, uint64_t* zero) const {
+    const uint32_t r = i < n ? perm[i] : DG_NONE;
+    *zero = r < n && ((round[r] >> bit) & 1) == 0;
+  }
+  __device__ void place(uint64_t i, uint64_t z, uint64_t zb) const {  // zb: the zeros before i
+    if (i >= n) return;
     const uint64_t zeros = pctl[mvk::PP_CTL_ZEROS];  // (the scan, an earlier launch)
     const uint64_t dst = z ? zb : zeros + (i - zb);
     if (dst < n) out[dst] = perm[i];
   }
-}
+};
 
 __global__ void __launch_bounds__(WG) k_pp_append(const uint64_t* __restrict__ slot, const uint64_t* __restrict__ round,
                                                   const uint32_t* __restrict__ auth, const uint64_t* __restrict__ tags,
@@ -308,53 +286,44 @@ __global__ void __launch_bounds__(WG) k_pp_stamp(PropQueue q, uint64_t cut, DagS
   if (lane == 0 && nbad) atomicAdd(ctl + mvk::IX_CTL_ERR, (u64)nbad);
 }
 
-__device__ inline void keep_of(const PropQueue& q, uint64_t cut, const uint32_t* stamp, uint64_t n_stamp, uint32_t counter,
-                               uint64_t j, bool* inc, bool* keep, bool* pay) {
-  *inc = *keep = *pay = false;
-  if (j >= cut) return;
-  const uint32_t kind = q.kind[j];
-  *pay = kind == mvk::PP_PAYLOAD;
-  if (kind != mvk::PP_INCLUDE) return;
-  const uint64_t s = q.slot[j];
-  *inc = true;
-  *keep = s < n_stamp && stamp[s] != counter;  // (a slot outside the table: k_pp_stamp counted it)
-}
-__global__ void __launch_bounds__(WG) k_pp_keep_count(PropQueue q, uint64_t cut, const uint32_t* __restrict__ stamp,
-                                                      uint64_t n_stamp, uint32_t counter, uint64_t* __restrict__ wg_a,
-                                                      uint64_t* __restrict__ wg_b, u64* __restrict__ pctl) {
-  const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  bool inc, keep, pay;
-  keep_of(q, cut, stamp, n_stamp, counter, j, &inc, &keep, &pay);
-  uint64_t ta, tb;
-  (void)wg_excl(keep, &ta);
-  (void)wg_excl(pay, &tb);
-  if (threadIdx.x == 0) {
-    wg_a[blockIdx.x] = ta;
-    wg_b[blockIdx.x] = tb;
+// the include entries below the cut that no stamp reached stay; weights: such an entry, a payload entry
+struct KeepEntries {
+  static constexpr int WEIGHTS = 2;
+  const u64* slots;
+  PropQueue q;
+  uint64_t qn, cut;
+  const uint32_t* stamp;
+  uint64_t n_stamp;
+  uint32_t counter;
+  uint64_t* includes;
+  uint64_t cap;
+  uint64_t* choice;
+  uint64_t cap_choice;
+  uint64_t* payloads;
+  uint64_t cap_p;
+  u64* pctl;
+  __device__ void weigh(uint64_t j, uint64_t* keep, uint64_t* pay) const {
+    *keep = *pay = 0;
+    if (j >= cut) return;
+    const uint32_t kind = q.kind[j];
+    *pay = kind == mvk::PP_PAYLOAD;
+    if (kind != mvk::PP_INCLUDE) return;
+    const uint64_t s = q.slot[j];
+    *keep = s < n_stamp && stamp[s] != counter;  // (a slot outside the table: k_pp_stamp counted it)
   }
-  wave_count_to(pctl + mvk::PP_CTL_NENT, inc);
-}
-__global__ void __launch_bounds__(WG) k_pp_keep_list(const u64* __restrict__ slots, PropQueue q, uint64_t qn, uint64_t cut,
-                                                     const uint32_t* __restrict__ stamp, uint64_t n_stamp, uint32_t counter,
-                                                     const uint64_t* __restrict__ base_a, const uint64_t* __restrict__ base_b,
-                                                     uint64_t* __restrict__ includes, uint64_t cap, uint64_t* __restrict__ choice,
-                                                     uint64_t cap_choice, uint64_t* __restrict__ payloads, uint64_t cap_p,
-                                                     u64* __restrict__ pctl) {
-  const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  bool inc, keep, pay;
-  keep_of(q, cut, stamp, n_stamp, counter, j, &inc, &keep, &pay);
-  uint64_t ta, tb;
-  const uint64_t ra = base_a[blockIdx.x] + wg_excl(keep, &ta);
-  const uint64_t rb = base_b[blockIdx.x] + wg_excl(pay, &tb);
-  if (keep) {
-    const uint64_t s = q.slot[j];  // (below n_stamp, the table's size: keep_of)
-    if (ra < cap)
-      for (int w = 0; w < 6; w++) includes[6 * ra + w] = slots[SLOT_WORDS * s + 2 + w];
-    if (ra < cap_choice) choice[ra] = s;
+  __device__ void place(uint64_t j, uint64_t keep, uint64_t ra, uint64_t pay, uint64_t rb) const {
+    if (keep) {
+      const uint64_t s = q.slot[j];  // (below n_stamp, the table's size: weigh)
+      if (ra < cap) copy_key(includes + 6 * ra, slots + SLOT_WORDS * s);
+      if (ra < cap_choice) choice[ra] = s;
+    }
+    if (pay && rb < cap_p) payloads[rb] = q.tag[j];
+    if (j == 0) pctl[mvk::PP_CTL_NEXT] = cut < qn ? q.tag[cut] : ~0ull;
+    // The include entries below the cut, kept or not: neither weight says it, so the kind is read again.
+    // It is counted here, in the list launch: this pass must never run with list = false.
+    wave_count_to(pctl + mvk::PP_CTL_NENT, j < cut && q.kind[j] == mvk::PP_INCLUDE);
   }
-  if (pay && rb < cap_p) payloads[rb] = q.tag[j];
-  if (j == 0) pctl[mvk::PP_CTL_NEXT] = cut < qn ? q.tag[cut] : ~0ull;
-}
+};
 
 __global__ void __launch_bounds__(WG) k_pp_shift(PropQueue q, PropQueue to, uint64_t cut, uint64_t qn) {
   const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
@@ -419,26 +388,6 @@ __global__ void __launch_bounds__(64) k_pp_record_map(DagStore d, uint64_t nb, c
   if (threadIdx.x == 0 && pctl[mvk::PP_CTL_APPENDED] && s < d.n_slots && nb < d.cap_b) d.map[s] = (uint32_t)nb;
 }
 
-__global__ void __launch_bounds__(WG) k_pp_reresolve(const u64* __restrict__ old, uint64_t n_old, IndexTable t,
-                                                     uint64_t* __restrict__ slotidx, uint64_t n, u64* __restrict__ ctl) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  bool bad = false;
-  if (i < n && slotidx[i] != DG_NO_SLOT) {
-    const uint64_t o = slotidx[i];
-    bad = o >= n_old;
-    if (!bad) {
-      uint64_t k[6];
-      for (int w = 0; w < 6; w++) k[w] = old[SLOT_WORDS * o + 2 + w];
-      const u64 s = pp_find(t, k, &bad);
-      bad = bad || s == DG_NO_SLOT;
-      slotidx[i] = bad ? DG_NO_SLOT : s;
-    } else {
-      slotidx[i] = DG_NO_SLOT;
-    }
-  }
-  wave_count_to(ctl + mvk::IX_CTL_ERR, bad);
-}
-
 }  // namespace mv::ix
 
 namespace mvk {
@@ -456,11 +405,8 @@ hipError_t launch_propose_resolve(const IndexTable& t, const uint64_t* rows, uin
 hipError_t launch_propose_sort_bit(const uint64_t* round, int bit, const uint32_t* perm, uint32_t* perm_out,
                                    uint64_t n, uint64_t* wg, uint64_t* pctl, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  const WgScan w = wg_scan_of(wg, n);
-  const dim3 g(grid_of(n)), b(WG);
-  hipLaunchKernelGGL(k_pp_bit_count, g, b, 0, s, round, bit, perm, n, w.count_a);
-  (void)launch_index_scan(w.count_a, index_groups(n), w.base_a, pctl + PP_CTL_ZEROS, nullptr, s);
-  hipLaunchKernelGGL(k_pp_bit_scatter, g, b, 0, s, round, bit, perm, perm_out, n, w.base_a, (const u64*)pctl);
+  compact_pass(SortBit{round, bit, perm, perm_out, n, (const u64*)pctl}, n, wg_scan_of(wg, n), pctl + PP_CTL_ZEROS, nullptr,
+               nullptr, s);
   return hipGetLastError();
 }
 
@@ -499,14 +445,9 @@ hipError_t launch_propose_keep(const IndexTable& t, const PropQueue& q, uint64_t
                                uint64_t cap_choice, uint64_t* payloads, uint64_t cap_p, uint64_t* wg, uint64_t* pctl,
                                uint64_t* ctl, hipStream_t s) {
   const uint64_t items = cut ? cut : 1;  // (lane 0 also notes the next tag)
-  const uint64_t nwg = index_groups(items);
-  const WgScan w = wg_scan_of(wg, items);
-  const dim3 g(grid_of(items)), b(WG);
-  hipLaunchKernelGGL(k_pp_keep_count, g, b, 0, s, q, cut, stamp, n_stamp, counter, w.count_a, w.count_b, (u64*)pctl);
-  (void)launch_index_scan(w.count_a, nwg, w.base_a, pctl + PP_CTL_NINC, nullptr, s);
-  (void)launch_index_scan(w.count_b, nwg, w.base_b, pctl + PP_CTL_NPAY, nullptr, s);
-  hipLaunchKernelGGL(k_pp_keep_list, g, b, 0, s, (const u64*)t.slots, q, qn, cut, stamp, n_stamp, counter, w.base_a, w.base_b,
-                     includes, cap, choice, cap_choice, payloads, cap_p, (u64*)pctl);
+  compact_pass(KeepEntries{(const u64*)t.slots, q, qn, cut, stamp, n_stamp, counter, includes, cap, choice, cap_choice, payloads,
+                           cap_p, (u64*)pctl},
+               items, wg_scan_of(wg, items), pctl + PP_CTL_NINC, pctl + PP_CTL_NPAY, nullptr, s);
   return hipGetLastError();
 }
 
@@ -528,13 +469,6 @@ hipError_t launch_propose_record(const IndexTable& t, const DagStore& d, uint64_
   hipLaunchKernelGGL(k_pp_record, dim3(grid_of(k ? k : 1)), dim3(WG), 0, s, (const u64*)t.slots, d, nb, ni, own, k, (u64*)pctl,
                      (u64*)ctl);
   hipLaunchKernelGGL(k_pp_record_map, dim3(1), dim3(64), 0, s, d, nb, own, (const u64*)pctl);
-  return hipGetLastError();
-}
-
-hipError_t launch_propose_reresolve(const uint64_t* old_slots, uint64_t n_old, const IndexTable& t, uint64_t* slotidx,
-                                    uint64_t n, uint64_t* ctl, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pp_reresolve, dim3(grid_of(n)), dim3(WG), 0, s, (const u64*)old_slots, n_old, t, slotidx, n, (u64*)ctl);
   return hipGetLastError();
 }
 

@@ -5,9 +5,9 @@
 //
 //   k_replay_select   one lane per entry: unknown tags and tag-3 payloads without a header become
 //                     the entry's status; counts the entries that carry a block per workgroup
-//   k_replay_scan     one workgroup: exclusive scan of the per-workgroup counts, the block total
+//   (k_ix_scan)       index.hip's scan of the per-workgroup counts, the block total
 //   k_replay_list     one lane per entry: the block's (offset, length, entry) at its scanned
-//                     position, so the list is in iteration order
+//                     position (index_dev.h's workgroup prefix), so the list is in iteration order
 //   k_replay_rows     one lane per listed block: the row from the block's first 56 bytes; a block
 //                     that does not parse, then an authority outside the committee, become the
 //                     entry's status (decode before authority, block_store.rs:73-74, 424-428)
@@ -23,20 +23,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels.h"
+#include "index_dev.h"
 #include "wal_entry.h"
 
 namespace mv {
 namespace rp {
 
-constexpr int WG = 256;
-constexpr int MAX_AUTH = 512;  // mv_set_committee's limit
+constexpr int WG = ix::WG;  // (the per-workgroup counts go through the index's scan)
 
 __device__ inline uint64_t ld64(const uint8_t* p) {
   uint64_t v;
   __builtin_memcpy(&v, p, 8);
   return v;
 }
+constexpr int MAX_AUTH = 512;  // mv_set_committee's limit
 
 __device__ inline bool carries_block(const uint64_t* pos, const uint32_t* tag, const uint32_t* len, const uint8_t* st,
                                      uint64_t e, uint64_t size, we::Entry& c) {
@@ -47,7 +47,7 @@ __device__ inline bool carries_block(const uint64_t* pos, const uint32_t* tag, c
 
 __global__ void __launch_bounds__(WG) k_replay_select(const uint64_t* __restrict__ pos, const uint32_t* __restrict__ tag,
                                                       const uint32_t* __restrict__ len, uint8_t* __restrict__ st,
-                                                      uint64_t n, uint64_t size, uint32_t* __restrict__ wgcount) {
+                                                      uint64_t n, uint64_t size, uint64_t* __restrict__ wgcount) {
   const uint64_t e = (uint64_t)blockIdx.x * WG + threadIdx.x;
   int blk = 0;
   if (e < n && st[e] == MV_WAL_OK) {
@@ -56,32 +56,7 @@ __global__ void __launch_bounds__(WG) k_replay_select(const uint64_t* __restrict
     blk = c.block;
   }
   const int cnt = __syncthreads_count(blk);
-  if (threadIdx.x == 0) wgcount[blockIdx.x] = (uint32_t)cnt;
-}
-
-// wgbase[g] = blocks of the workgroups before g; *nb = all of them
-__global__ void __launch_bounds__(1024) k_replay_scan(const uint32_t* __restrict__ wgcount, uint64_t nwg,
-                                                      uint64_t* __restrict__ wgbase, uint64_t* __restrict__ nb) {
-  __shared__ uint64_t part[1024];
-  const uint64_t per = (nwg + 1023) / 1024;
-  const uint64_t lo = per * threadIdx.x < nwg ? per * threadIdx.x : nwg;
-  const uint64_t hi = lo + per < nwg ? lo + per : nwg;
-  uint64_t sum = 0;
-  for (uint64_t g = lo; g < hi; g++) sum += wgcount[g];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {  // inclusive scan of the 1024 partial sums
-    const uint64_t v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint64_t acc = part[threadIdx.x] - sum;
-  for (uint64_t g = lo; g < hi; g++) {
-    wgbase[g] = acc;
-    acc += wgcount[g];
-  }
-  if (threadIdx.x == 1023) *nb = part[1023];
+  if (threadIdx.x == 0) wgcount[blockIdx.x] = (uint64_t)cnt;
 }
 
 // cap: the lists' length (the host sizes them by the entry count)
@@ -90,18 +65,12 @@ __global__ void __launch_bounds__(WG) k_replay_list(const uint64_t* __restrict__
                                                     uint64_t n, uint64_t size, const uint64_t* __restrict__ wgbase,
                                                     uint64_t* __restrict__ blk_off, uint64_t* __restrict__ blk_len,
                                                     uint64_t* __restrict__ blk_ent, uint64_t cap) {
-  __shared__ uint32_t wave_cnt[WG / 64];
   const uint64_t e = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x / 64;
   we::Entry c{};
   const bool blk = e < n && carries_block(pos, tag, len, st, e, size, c);
-  const unsigned long long m = __ballot(blk);
-  if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
-  if (!blk) return;
-  uint64_t r = wgbase[blockIdx.x] + (uint64_t)__popcll(m & ((1ull << lane) - 1));
-  for (uint32_t w = 0; w < wave; w++) r += wave_cnt[w];
-  if (r >= cap) return;
+  uint64_t tot;
+  const uint64_t r = wgbase[blockIdx.x] + ix::wg_excl(blk, &tot);
+  if (!blk || r >= cap) return;
   blk_off[r] = c.off;
   blk_len[r] = c.len;
   blk_ent[r] = e;
@@ -201,13 +170,13 @@ namespace mvk {
 
 uint64_t replay_groups(uint64_t n) { return (n + mv::rp::WG - 1) / mv::rp::WG; }
 
-hipError_t launch_replay_select(const ReplayEntries& en, uint64_t size, uint32_t* wgcount, uint64_t* wgbase,
+hipError_t launch_replay_select(const ReplayEntries& en, uint64_t size, uint64_t* wgcount, uint64_t* wgbase,
                                 uint64_t* nb, hipStream_t s) {
   if (en.n == 0) return hipSuccess;
   const uint64_t nwg = replay_groups(en.n);
   hipLaunchKernelGGL(mv::rp::k_replay_select, dim3((uint32_t)nwg), dim3(mv::rp::WG), 0, s, en.pos, en.tag, en.len,
                      en.status, en.n, size, wgcount);
-  hipLaunchKernelGGL(mv::rp::k_replay_scan, dim3(1), dim3(1024), 0, s, wgcount, nwg, wgbase, nb);
+  (void)launch_index_scan(wgcount, nwg, wgbase, nb, nullptr, s);
   return hipGetLastError();
 }
 

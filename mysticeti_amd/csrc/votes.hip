@@ -193,39 +193,18 @@ __global__ void __launch_bounds__(WG) k_vt_scan(VoteCall c, u64* __restrict__ ct
 }
 
 // ---------------------------------------------------------------- the scan of u32 counts
-__global__ void __launch_bounds__(WG) k_vt_wgsum(const uint32_t* __restrict__ v, uint64_t n, uint64_t* __restrict__ wgcount) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  (void)wg_excl(i < n ? v[i] : 0, &tot);
-  if (threadIdx.x == 0) wgcount[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(WG) k_vt_wgexcl(const uint32_t* __restrict__ v, uint64_t n,
-                                                  const uint64_t* __restrict__ wgbase, uint64_t* __restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  uint64_t tot;
-  const uint64_t ex = wg_excl(i < n ? v[i] : 0, &tot);
-  if (i < n) out[i] = wgbase[blockIdx.x] + ex;
-}
+struct ScanU32 {
+  static constexpr int WEIGHTS = 1;
+  const uint32_t* v;
+  uint64_t n;
+  uint64_t* out;
+  __device__ void weigh(uint64_t i, uint64_t* w) const { *w = i < n ? v[i] : 0; }
+  __device__ void place(uint64_t i, uint64_t, uint64_t ex) const {
+    if (i < n) out[i] = ex;
+  }
+};
 
 // ---------------------------------------------------------------- rows
-// the slot of key k, read-only (nothing writes the table in a launch that calls it)
-__device__ inline bool find_slot(const IndexTable& t, const uint64_t k[6], uint64_t* at, bool* fail) {
-  uint64_t start, tag;
-  hash_key(t, k, &start, &tag);
-  uint64_t p = start;
-  for (uint64_t dist = 0; dist <= t.mask; dist++, p = (p + 1) & t.mask) {
-    const u64* slot = t.slots + SLOT_WORDS * p;
-    const u64 g = slot[0];
-    if (g == 0) return false;
-    if (g == tag && key_eq(slot, k)) {
-      *at = p;
-      return true;
-    }
-  }
-  *fail = true;
-  return false;
-}
-
 __global__ void __launch_bounds__(WG) k_vt_rows(VoteStore v, VoteCall c, const u64* __restrict__ item, u64* __restrict__ ctl) {
   const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
   bool brk = false;
@@ -300,10 +279,10 @@ struct EmitF {
     run1 = k + 1;
   }
   __device__ void target(const uint64_t* key, uint64_t s, uint64_t e) {
-    uint64_t p = 0;
-    bool fail = false;
-    uint32_t row = VT_NO_ROW, kind = mvk::VT_KIND_VOTE;
-    if (v.t.slots && find_slot(v.t, key, &p, &fail)) row = v.rowmap[p];
+    bool fail;
+    uint32_t probe, row = VT_NO_ROW, kind = mvk::VT_KIND_VOTE;
+    const u64 p = find_slot(v.t, key, &probe, &fail);
+    if (p != DG_NO_SLOT) row = v.rowmap[p];
     if (fail) vt_err(ctl);
     uint64_t cs = 0, ce = 0;
     if (row != VT_NO_ROW && row < v.cap_rows) {
@@ -553,23 +532,13 @@ __global__ void __launch_bounds__(WG) k_vt_move(VoteStore v, uint64_t nrows, Vot
     return;
   }
   if (lane == 0) {
-    uint64_t k[6], start, tag;
+    uint64_t k[6];
 #pragma unroll
     for (int w = 0; w < 6; w++) k[w] = v.row_key[6 * row + w];
-    hash_key(q.t, k, &start, &tag);
-    uint64_t p = start, dist = 0;
-    bool done = false;
-    for (; dist <= q.t.mask; dist++, p = (p + 1) & q.t.mask) {
-      u64* slot = q.t.slots + SLOT_WORDS * p;
-      if (atomicCAS(slot, 0ull, (u64)tag) != 0) continue;
-#pragma unroll
-      for (int w = 0; w < 6; w++) slot[2 + w] = k[w];
-      slot[1] = 1;
-      q.rowmap[p] = (uint32_t)nr;
-      done = true;
-      break;
-    }
-    if (!done) vt_err(ctl);
+    uint32_t probe;
+    const u64 p = claim_fresh(q.t, k, 1, &probe);
+    if (p != DG_NO_SLOT) q.rowmap[p] = (uint32_t)nr;
+    else vt_err(ctl);
 #pragma unroll
     for (int w = 0; w < 6; w++) q.row_key[6 * nr + w] = k[w];
     q.row_base[nr] = nb;
@@ -592,11 +561,7 @@ hipError_t launch_votes_scan_u32(const uint32_t* v, uint64_t n, uint64_t* out, u
     if (hipMemsetAsync(total, 0, 8, s) != hipSuccess) return hipGetLastError();
     return hipSuccess;
   }
-  const WgScan w = wg_scan_of(wg, n);
-  const dim3 g(grid_of(n)), b(WG);
-  hipLaunchKernelGGL(k_vt_wgsum, g, b, 0, s, v, n, w.count_a);
-  (void)launch_index_scan(w.count_a, index_groups(n), w.base_a, total, running, s);
-  hipLaunchKernelGGL(k_vt_wgexcl, g, b, 0, s, v, n, w.base_a, out);
+  compact_pass(ScanU32{v, n, out}, n, wg_scan_of(wg, n), total, nullptr, running, s);
   return hipGetLastError();
 }
 

@@ -310,6 +310,17 @@ def test_one_parent_releases_more_than_a_workgroup(wide_eng, wide):
     assert [IM.words_ref(r[:6]) for r in got.connected[1:]] == want
 
 
+def test_groups_across_a_workgroup_edge(wide_eng, wide):
+    """257 blocks in groups of three: the group numbers of the second workgroup's block stand behind
+    the first workgroup's heads. A bad signature at block 256 drops block 255, its group's other block."""
+    corpus, _ = wide
+    three = wide_model(wide_eng, wide)
+    blocks = list(corpus[0][:257])
+    blocks[256] = bad_signature(blocks[256])
+    got, _ = connect(wide_eng, three, corpus, blocks, [i // 3 for i in range(257)], "grouped")
+    assert got.blk_state.tolist() == [M.ACC_NEW] * 255 + [M.ACC_DROPPED, M.ACC_REJECTED]
+
+
 # ---------------------------------------------------------------- 8. the device call
 def dev_connect(e, blocks, groups, cap, cap_rows, pad=16):
     """mv_dev_connect_blocks on a device buffer that ends `pad` bytes after the last block."""
