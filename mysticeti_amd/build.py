@@ -29,7 +29,7 @@ SOURCES = ["kernels.hip", "batch.hip", "comb.hip", "ingest.hip", "blake2b_quad.h
 SOURCE_FLAGS = {"batch.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "blake2b_lane.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "ingest.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-HEADERS = ["asm_ops.h", "fe25519.h", "ge25519.h", "hash_dev.h", "scalar25519.h", "kernels.h", "block_codec.h", "tables.h", "carry32.h", "comb.h", "quad25519.h", "fe_q4.h", "fe_r16.h", "blake2b_quad.h", "block_verdict.h", "bincode_walk.h", "ingest_dev.h", "pt_r16.h", "frame_walk.h", "wal_entry.h", "block_ref.h", "index_dev.h", "dev_resources.h", "engine_internal.h"]
+HEADERS = ["asm_ops.h", "fe25519.h", "ge25519.h", "hash_dev.h", "scalar25519.h", "kernels.h", "block_codec.h", "tables.h", "carry32.h", "comb.h", "quad25519.h", "fe_q4.h", "fe_r16.h", "blake2b_quad.h", "block_verdict.h", "bincode_walk.h", "ingest_dev.h", "ingest_lane.h", "votes_walk.h", "pt_r16.h", "frame_walk.h", "wal_entry.h", "block_ref.h", "index_dev.h", "dev_resources.h", "engine_internal.h"]
 
 
 def _newer(target: str, deps) -> bool:

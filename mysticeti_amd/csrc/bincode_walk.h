@@ -1,7 +1,7 @@
 // The straight-line walk of one StatementBlock's bincode (bincode 1.3.3 defaults, data.rs:43-52;
 // types.rs:93-114) that emits the signed pre-image (crypto.rs:85-128 with the CryptoHash encodings
 // of crypto.rs:150-170, types.rs:661-691, 751-755), stated once for every one-lane user: the
-// verify ingest's ingest_lane (ingest_dev.h) and both seal kernels (seal.hip). What parses here is
+// verify ingest's ingest_lane (ingest_lane.h) and both seal kernels (seal.hip). What parses here is
 // what the library seals and what it accepts; block_codec.cpp (host) and oracle/ are the second and
 // third opinions tests/test_gpu_ingest.py holds it to.
 //
