@@ -851,6 +851,85 @@ mv_status mv_seal_blocks(mv_ctx* ctx, uint8_t* buf, const uint64_t* off, const u
                          uint8_t* status /* n, MV_SEAL_* */, uint8_t* msg_digest /* n x 32 or NULL */,
                          uint8_t* block_digest /* n x 32 or NULL */);
 
+/* ---- encoding blocks ----
+ * What stands between mv_propose_take and mv_seal_blocks: the block of Core::try_new_block written
+ * as bytes. Replaces the include and statement vectors of core.rs:264-291 (the own last block first,
+ * then the take's choice; statements.extend(payload) per taken payload), the struct of
+ * StatementBlock::new_with_signer (types.rs:93-114, 155-218) and Data::new's bincode::serialize
+ * (data.rs:43-52). The digest and signature fields come out as the zero placeholders mv_seal_blocks
+ * overwrites; MV_ENCODE_SEAL seals in the same call. Stateless: no index, store or clock changes, no
+ * committee is needed. Runs on the context's first device and takes the context in turn.
+ *
+ * Inputs, for n blocks:
+ *   heads        n x 10 words: 0 authority, 1 round, 2 / 3 the low / high half of
+ *                meta_creation_time_ns, 4 epoch, 5 epoch marker (0 / 1), 6 the first row of `includes`,
+ *                7 the include count k, 8 the first entry of the payload list, 9 the payload count
+ *   includes     m x 6 words: the reference rows mv_propose_take writes and mv_propose_own reads. The
+ *                caller puts the own last block's reference in row 0 of a block's run and the take's
+ *                output behind it (core.rs:264-271)
+ *   payload_buf, payload_off[p], payload_len[p]: payload j is payload_buf[payload_off[j],
+ *                payload_off[j] + payload_len[j]), one bincode::serialize(&Vec<BaseStatement>) string
+ *                as run_block_handler writes it into a tag-2 WAL entry (core.rs:217-224): a u64 count,
+ *                then the statements; at any byte offset. A block's statements are the bodies of its
+ *                payloads in list order under one count, the sum of theirs. Payloads may be shared
+ *                between blocks and may overlap.
+ * An OK block's bytes: authority, round, 32, 32 zero bytes; k; k x (authority, round, 32, digest); the
+ * statement count; the payload bodies; time low, time high; the marker byte; the epoch; 64, 64 zero
+ * bytes -- 169 + 56 k + sum(payload_len - 8) bytes. Blocks lie one behind the other in `out`, each
+ * starting on an 8-byte boundary; the 0-7 bytes between a block's end and the next start are
+ * written as zero. out_off[i] is where block i starts, out_len[i] its length, *out_bytes the whole
+ * span (the padding of the last block included). A block that is not MV_ENCODE_OK has out_len 0, takes
+ * no space (its out_off is where the next block starts) and changes nothing for its neighbours. */
+#define MV_ENCODE_OK 0
+#define MV_ENCODE_BAD_HEAD 1    /* marker > 1, or the include run leaves [0, m), or the payload run leaves [0, p) */
+#define MV_ENCODE_BAD_PAYLOAD 2 /* a payload of the block leaves payload_buf, fails the statement walk
+                                   (types.rs:100-114, what MV_BLOCK_PARSE_ERROR fails), or the walk does not end on
+                                   its last byte: trailing bytes would end up between two payloads' statements */
+#define MV_ENCODE_TOO_LONG 3    /* longer than MV_ENCODE_MAX_LEN: the panic of core.rs:300-306 */
+/* wal.rs:107 at the production map size (wal.rs:96-97, 110): MAX_ENTRY_SIZE / 2 =
+ * (0x1000000 - 16) / 2 */
+#define MV_ENCODE_MAX_LEN 8388600
+#define MV_ENCODE_SEAL 1u /* flags: seal the encoded blocks in place (mv_seal_blocks' body) */
+#define MV_ENCODE_LINK 2u /* flags, with MV_ENCODE_SEAL: MV_SEAL_LINK */
+/* status[i] = MV_ENCODE_*, checked in the order above. If *out_bytes exceeds cap the call writes no
+ * byte of `out` and does not seal, but status, out_off, out_len and *out_bytes are written: call again
+ * with room (the rule of MV_PROPOSE_SHORT); with MV_ENCODE_SEAL every seal_status is then
+ * MV_SEAL_PARSE_ERROR and the digests are zero.
+ * MV_ENCODE_SEAL: seeds, n_auth, seal_status, msg_digest and block_digest are mv_seal_blocks' (the
+ * digest arrays may be NULL), run over the encoded image before anything is copied back. A block that is
+ * not MV_ENCODE_OK is an empty span to the seal: its seal_status is MV_SEAL_PARSE_ERROR, its digests
+ * are zero, and under MV_ENCODE_LINK the includes that name it keep their bytes. Everything else the
+ * seal's comment says holds: MV_SEAL_UNLINKED, MV_SEAL_UNKNOWN_AUTHOR, rounds out of order under LINK
+ * are MV_E_INVALID_ARG (then `out` is not written; status, out_off, out_len and *out_bytes are), the
+ * seeds and keys are zeroed on the device. Without MV_ENCODE_SEAL the five arguments are ignored.
+ * n, m and p may be 0; cap may be 0 (`out` may then be NULL): the call sizes. */
+mv_status mv_encode_blocks(mv_ctx* ctx, const uint64_t* heads /* n x 10 */, uint32_t n,
+                           const uint64_t* includes /* m x 6 */, uint64_t m, const uint8_t* payload_buf,
+                           uint64_t payload_bytes, const uint64_t* payload_off /* p */,
+                           const uint64_t* payload_len /* p */, uint64_t p, uint32_t flags,
+                           const uint8_t* seeds /* n_auth x 32 */, uint32_t n_auth, uint8_t* out, uint64_t cap,
+                           uint64_t* out_off /* n */, uint64_t* out_len /* n */, uint8_t* status /* n */,
+                           uint64_t* out_bytes, uint8_t* seal_status /* n */, uint8_t* msg_digest /* n x 32 or NULL */,
+                           uint8_t* block_digest /* n x 32 or NULL */);
+/* mv_encode_blocks with every array in HBM of the context's first device (*out_bytes is the
+ * host's). The u64 arrays and d_payload_buf are 8-byte aligned, d_seeds 4-byte; 16 bytes past
+ * payload_bytes are readable (payloads are read as whole aligned words); d_out is 8-byte aligned with
+ * 16 readable bytes past cap, as mv_dev_seal_blocks asks. The host-buffer call is a copy in, this
+ * call and a copy out. Synchronises `stream` once, for the total; without MV_ENCODE_SEAL the bytes are
+ * written behind that, in stream order (the next encode call on the context waits for them before it
+ * reuses the call's scratch, and reports a bounds check they failed as MV_E_HIP); with it the seal
+ * synchronises as mv_dev_seal_blocks does. The image is encoded in d_out before it is sealed there: after
+ * MV_E_INVALID_ARG for rounds out of order under MV_ENCODE_LINK d_out holds the encoded blocks with
+ * their zero placeholders, unsealed (the host-buffer call does not copy them back), and
+ * d_seal_status the seal's first pass. n <= 2^31 - 1, p <= 2^32 - 1. */
+mv_status mv_dev_encode_blocks(mv_ctx* ctx, int device, const uint64_t* d_heads, uint32_t n,
+                               const uint64_t* d_includes, uint64_t m, const uint8_t* d_payload_buf,
+                               uint64_t payload_bytes, const uint64_t* d_payload_off, const uint64_t* d_payload_len,
+                               uint64_t p, uint32_t flags, const uint8_t* d_seeds, uint32_t n_auth, uint8_t* d_out,
+                               uint64_t cap, uint64_t* d_out_off, uint64_t* d_out_len, uint8_t* d_status,
+                               uint64_t* out_bytes, uint8_t* d_seal_status, uint8_t* d_msg_digest,
+                               uint8_t* d_block_digest, void* stream);
+
 /* ---- transaction votes: fast-path certificates per block ----
  * What BlockHandler::handle_blocks does with the blocks add_blocks returns (core.rs:171-207,
  * block_handler.rs:146-190): TransactionAggregator::process_block (committee.rs:263-482) over a

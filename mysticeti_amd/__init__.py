@@ -55,7 +55,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -88,7 +88,7 @@ EXPORTS = [
     "mv_commit_leaders", "mv_dev_commit_leaders", "mv_wal_recover", "mv_dev_dag_seed_rows",
     "mv_linearize", "mv_dev_linearize", "mv_linearize_mark", "mv_linearize_stats",
     "mv_propose_reserve", "mv_propose_add", "mv_dev_propose_add", "mv_propose_take", "mv_propose_own", "mv_propose_stats",
-    "mv_seal_blocks", "mv_dev_seal_blocks",
+    "mv_seal_blocks", "mv_dev_seal_blocks", "mv_encode_blocks", "mv_dev_encode_blocks",
     "mv_votes_reserve", "mv_votes_clear", "mv_votes_stats", "mv_aggregate_votes", "mv_dev_aggregate_votes",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
@@ -96,6 +96,13 @@ EXPORTS = [
 SEAL_STATUS = ["OK", "PARSE_ERROR", "UNKNOWN_AUTHOR", "UNLINKED"]
 SEAL_OK, SEAL_PARSE_ERROR, SEAL_UNKNOWN_AUTHOR, SEAL_UNLINKED = range(4)
 SEAL_LINK = 1
+# per-block outcomes of mv_encode_blocks, its length limit (wal.rs:107: MAX_ENTRY_SIZE / 2), its flags and the
+# words of a head row
+ENCODE_STATUS = ["OK", "BAD_HEAD", "BAD_PAYLOAD", "TOO_LONG"]
+ENCODE_OK, ENCODE_BAD_HEAD, ENCODE_BAD_PAYLOAD, ENCODE_TOO_LONG = range(4)
+ENCODE_MAX_LEN = 8388600
+ENCODE_SEAL, ENCODE_LINK = 1, 2
+ENCODE_HEAD_WORDS = 10
 # per-block outcomes of mv_aggregate_votes, the flag bits of a block's fourth count word, the call's flag
 VOTES_STATUS = ["OK", "PARSE_ERROR", "UNKNOWN_AUTHOR"]
 VOTES_OK, VOTES_PARSE_ERROR, VOTES_UNKNOWN_AUTHOR = range(3)
@@ -154,6 +161,37 @@ class MvError(RuntimeError):
         self.code = code
 
 
+class EncodeResult(NamedTuple):
+    """Engine.encode_blocks: the image, where each block starts and how long it is, MV_ENCODE_* per
+    block, the whole span; with seal=True MV_SEAL_* per block and both digests, else None."""
+    buf: np.ndarray
+    offs: np.ndarray
+    lens: np.ndarray
+    status: np.ndarray
+    out_bytes: int
+    seal_status: Optional[np.ndarray]
+    msg_digest: Optional[np.ndarray]
+    block_digest: Optional[np.ndarray]
+
+
+def encode_bound(heads: np.ndarray, m: int, payload_len: np.ndarray) -> int:
+    """An upper bound of mv_encode_blocks' *out_bytes from the heads and the payload lengths alone: a
+    head whose runs are inside gives 176 + 56 k + the lengths of its payloads, any other nothing."""
+    heads = np.asarray(heads, dtype=np.uint64).reshape(-1, ENCODE_HEAD_WORDS)
+    if heads.shape[0] == 0:
+        return 0
+    p = int(payload_len.shape[0])
+    cum = np.zeros(p + 1, dtype=np.float64)
+    cum[1:] = np.cumsum(payload_len.astype(np.float64))
+    inc0, k, pay0, np_ = (heads[:, w].astype(np.float64) for w in (6, 7, 8, 9))
+    ok = (inc0 + k <= m) & (pay0 + np_ <= p)
+    lo = np.where(ok, pay0, 0).astype(np.int64)
+    hi = np.where(ok, pay0 + np_, 0).astype(np.int64)
+    size = np.where(ok, 176 + 56 * k + cum[hi] - cum[lo], 0)
+    size = np.minimum(size, ENCODE_MAX_LEN + 8)
+    return int(size.sum())
+
+
 class _Config(ctypes.Structure):
     _fields_ = [("device_mask", ctypes.c_uint32), ("max_batch", ctypes.c_uint32), ("flags", ctypes.c_uint32),
                 ("shards_per_device", ctypes.c_uint32)]
@@ -197,6 +235,10 @@ def load_library(path: str = LIB_PATH):
     lib.mv_dev_ed25519_sign.argtypes = [vp, ctypes.c_int, vp, vp, u32, vp, vp, vp]
     lib.mv_seal_blocks.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
     lib.mv_dev_seal_blocks.argtypes = [vp, ctypes.c_int, vp, u64, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp]
+    lib.mv_encode_blocks.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, vp, u64, u32, vp, u32, vp, u64, vp, vp, vp, vp,
+                                     vp, vp, vp]
+    lib.mv_dev_encode_blocks.argtypes = [vp, ctypes.c_int, vp, u32, vp, u64, vp, u64, vp, vp, u64, u32, vp, u32, vp, u64,
+                                         vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mv_votes_reserve.argtypes = [vp, u64, u64]
     lib.mv_votes_clear.argtypes = [vp]
     lib.mv_votes_stats.argtypes = [vp, vp]
@@ -462,6 +504,82 @@ class Engine:
             d_off.shape[0], vp(d_seeds.data_ptr()), d_seeds.shape[0], SEAL_LINK if link else 0,
             vp(d_status.data_ptr()), vp(d_md.data_ptr()) if d_md is not None else None,
             vp(d_bd.data_ptr()) if d_bd is not None else None, vp(stream_handle or None)), "mv_dev_seal_blocks")
+
+    # ---- encoding blocks (core.rs:264-291, types.rs:93-114, data.rs:43-52) ----
+    def encode_blocks(self, heads, includes, payloads, seal: bool = False, link: bool = False, seeds=None,
+                      cap: Optional[int] = None, out: Optional[np.ndarray] = None) -> "EncodeResult":
+        """The bincode of Core::try_new_block's blocks (mv_encode_blocks). heads: n x 10 words
+        (authority, round, time low, time high, epoch, marker, first include row, include count,
+        first payload, payload count); includes: m x 6 reference words, the own last block first in a
+        block's run; payloads: a list of bincode::serialize(&Vec<BaseStatement>) strings (packed back
+        to back here) or (buf, off, len) arrays. seal=True runs mv_seal_blocks' body on the image
+        (seeds: n_auth x 32), link=True with MV_SEAL_LINK. cap: the room for the blocks (default: an
+        upper bound from the heads and payload lengths); out: a uint8 array to write into (cap =
+        its size). Returns EncodeResult; when out_bytes > cap nothing was written or sealed."""
+        heads = np.ascontiguousarray(heads, dtype=np.uint64).reshape(-1, ENCODE_HEAD_WORDS)
+        includes = np.ascontiguousarray(includes, dtype=np.uint64).reshape(-1, 6)
+        if isinstance(payloads, tuple):
+            pbuf, poff, plen = payloads
+            pbuf = np.ascontiguousarray(pbuf, dtype=np.uint8)
+            poff = np.ascontiguousarray(poff, dtype=np.uint64)
+            plen = np.ascontiguousarray(plen, dtype=np.uint64)
+        else:
+            plen = np.array([len(x) for x in payloads], dtype=np.uint64)
+            poff = np.zeros(len(payloads), dtype=np.uint64)
+            if len(payloads) > 1:
+                poff[1:] = np.cumsum(plen)[:-1]
+            pbuf = np.frombuffer(b"".join(payloads), dtype=np.uint8)
+        n, m, p = heads.shape[0], includes.shape[0], poff.shape[0]
+        if out is not None:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and
+                    out.flags.writeable):
+                raise ValueError("out: a writable contiguous uint8 array")
+            cap = out.shape[0] if cap is None else int(cap)
+            if cap > out.shape[0]:
+                raise ValueError("cap reaches past out")
+        else:
+            if cap is None:
+                cap = encode_bound(heads, m, plen)
+            out = np.zeros(int(cap), dtype=np.uint8)
+        if link and not seal:
+            raise ValueError("link=True needs seal=True")
+        flags = (ENCODE_SEAL if seal else 0) | (ENCODE_LINK if link else 0)
+        seeds = _u8(seeds, 32) if seeds is not None else np.zeros((0, 32), dtype=np.uint8)
+        offs = np.zeros(n, dtype=np.uint64)
+        lens = np.zeros(n, dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8)
+        total = ctypes.c_uint64(0)
+        sst = np.zeros(n, dtype=np.uint8) if seal else None
+        md = np.zeros((n, 32), dtype=np.uint8) if seal else None
+        bd = np.zeros((n, 32), dtype=np.uint8) if seal else None
+        self._check(self.lib.mv_encode_blocks(
+            self.ctx, _p(heads), n, _p(includes) if m else None, m, _p(pbuf) if pbuf.shape[0] else None, pbuf.shape[0],
+            _p(poff) if p else None, _p(plen) if p else None, p, flags, _p(seeds) if seeds.shape[0] else None,
+            seeds.shape[0], _p(out) if cap else None, int(cap), _p(offs), _p(lens), _p(st), ctypes.byref(total), _p(sst),
+            _p(md), _p(bd)), "mv_encode_blocks")
+        return EncodeResult(out, offs, lens, st, int(total.value), sst, md, bd)
+
+    def dev_encode_blocks(self, device: int, d_heads, d_includes, d_payload_buf, payload_bytes: int, d_payload_off,
+                          d_payload_len, d_out, cap: int, d_out_off, d_out_len, d_status, seal: bool = False,
+                          link: bool = False, d_seeds=None, d_seal_status=None, d_md=None, d_bd=None,
+                          stream_handle: int = 0) -> int:
+        """mv_encode_blocks on HBM-resident arrays (torch tensors: int64 heads [n, 10], includes [m, 6],
+        payload offsets and lengths; uint8 payload bytes padded by 16 bytes past payload_bytes and an
+        image padded by 16 bytes past cap). Returns *out_bytes. Synchronises the stream for the total."""
+        vp = ctypes.c_void_p
+
+        def ptr(t):
+            return vp(t.data_ptr()) if t is not None and t.numel() else None
+
+        flags = (ENCODE_SEAL if seal else 0) | (ENCODE_LINK if link else 0)
+        total = ctypes.c_uint64(0)
+        self._check(self.lib.mv_dev_encode_blocks(
+            self.ctx, device, ptr(d_heads), d_heads.shape[0], ptr(d_includes), d_includes.shape[0], ptr(d_payload_buf),
+            int(payload_bytes), ptr(d_payload_off), ptr(d_payload_len), d_payload_off.shape[0], flags, ptr(d_seeds),
+            d_seeds.shape[0] if d_seeds is not None else 0, ptr(d_out), int(cap), ptr(d_out_off), ptr(d_out_len),
+            ptr(d_status), ctypes.byref(total), ptr(d_seal_status), ptr(d_md), ptr(d_bd), vp(stream_handle or None)),
+            "mv_dev_encode_blocks")
+        return int(total.value)
 
     # ---- transaction votes (committee.rs:263-482) ----
     def votes_reserve(self, blocks: int, cells: int):

@@ -144,6 +144,79 @@ def build_rounds_sealed(engine, rounds: int, n_auth: int, seeds: Sequence[bytes]
     return [raw[int(o): int(o) + int(l)] for o, l in zip(offs, lens)]
 
 
+def _le_bytes(values, width: int) -> np.ndarray:
+    """values (any integer array) as rows of `width` little-endian bytes."""
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    return v.view(np.uint8).reshape(v.shape + (8,))[..., :width]
+
+
+def encoded_inputs(rounds: int, n_auth: int, n_inc: int, n_vr: int, with_tx: bool, epoch: int = 0):
+    """The DAG of build_rounds_sealed as the inputs of Engine.encode_blocks, for all rounds at once and
+    without a per-block loop: (heads [n, 10], includes [n k, 6], (payload bytes, offsets, lengths)).
+    Block (r, a) is row (r - 1) n_auth + a; its includes are the own block of round r - 1 first, then
+    the lowest other authorities (digest words: genesis' for round 1, zero above: the seal links them);
+    its one payload is build_rounds_sealed's statements (none: no payload at all)."""
+    n, k = rounds * n_auth, min(n_inc, n_auth)
+    gen = genesis_refs(n_auth, epoch)
+    gen_words = np.array([struct.unpack("<4Q", g[2]) for g in gen], dtype=np.uint64).reshape(n_auth, 4)
+    a = np.tile(np.arange(n_auth, dtype=np.uint64), rounds)
+    r = np.repeat(np.arange(1, rounds + 1, dtype=np.uint64), n_auth)
+    n_st = (1 if with_tx else 0) + n_vr
+    heads = np.zeros((n, 10), dtype=np.uint64)
+    heads[:, 0], heads[:, 1], heads[:, 2], heads[:, 4] = a, r, r * np.uint64(10**8) + a, epoch
+    heads[:, 6], heads[:, 7] = np.arange(n, dtype=np.uint64) * np.uint64(k), k
+    if n_st:
+        heads[:, 8], heads[:, 9] = np.arange(n, dtype=np.uint64), 1
+    # include authorities of seat s: s, then the others in ascending order
+    j = np.arange(1, k, dtype=np.int64)[None, :]
+    seat = np.arange(n_auth, dtype=np.int64)[:, None]
+    inc_auth = np.concatenate([seat, np.where(j - 1 < seat, j - 1, j)], axis=1)  # [n_auth, k]
+    includes = np.zeros((rounds, n_auth, k, 6), dtype=np.uint64)
+    includes[..., 0] = inc_auth[None]
+    includes[..., 1] = np.arange(rounds, dtype=np.uint64)[:, None, None]
+    if rounds:
+        includes[0, :, :, 2:] = gen_words[inc_auth]
+    includes = includes.reshape(n * k, 6)
+    if not n_st:
+        return heads, includes, (np.zeros(0, np.uint8), np.zeros(0, np.uint64), np.zeros(0, np.uint64))
+    size = 8 + (524 if with_tx else 0) + 76 * n_vr
+    pay = np.zeros((n, size), dtype=np.uint8)
+    pay[:, 0:8] = _le_bytes(np.uint64(n_st), 8)
+    at = 8
+    if with_tx:  # Share(config4_tx(r, a)): tag 0, length 512, 8-B ts || 8-B rand || zeros
+        pay[:, at + 4:at + 12] = _le_bytes(np.uint64(512), 8)
+        pay[:, at + 12:at + 20] = _le_bytes(np.uint64(1_700_000_000_000) + r, 8)
+        pay[:, at + 20:at + 28] = _le_bytes(r * np.uint64(1_000_003) + a * np.uint64(7919), 8)
+        at += 524
+    if n_vr:  # VoteRange(gen[(a + 1 + v) % n_auth], 0, 1 + v % 7): the same for every round
+        v = np.arange(n_vr, dtype=np.int64)[None, :]
+        target = (seat + 1 + v) % n_auth  # [n_auth, n_vr]
+        vr = np.zeros((n_auth, n_vr, 76), dtype=np.uint8)
+        vr[..., 0] = 2
+        vr[..., 4:12] = _le_bytes(target, 8)
+        vr[..., 20:28] = _le_bytes(np.uint64(32), 8)
+        vr[..., 28:60] = gen_words[target].view(np.uint8).reshape(n_auth, n_vr, 32)
+        vr[..., 68:76] = _le_bytes(1 + v % 7 + 0 * seat, 8)
+        pay[:, at:] = np.tile(vr.reshape(n_auth, 76 * n_vr), (rounds, 1))
+    offs = np.arange(n, dtype=np.uint64) * np.uint64(size)
+    return heads, includes, (pay.reshape(-1), offs, np.full(n, size, dtype=np.uint64))
+
+
+def build_rounds_encoded(engine, rounds: int, n_auth: int, seeds: Sequence[bytes], n_inc: int, n_vr: int,
+                         with_tx: bool, epoch: int = 0) -> List[bytes]:
+    """build_rounds_sealed's DAG, byte for byte, without the host encode: the heads, include rows and
+    payloads of all rounds are numpy arrays (encoded_inputs), and one
+    Engine.encode_blocks(seal=True, link=True) call writes the bincode, signs, digests and links it on
+    the GPU (core.rs:264-291, types.rs:93-114, 155-218, data.rs:43-52)."""
+    heads, includes, payloads = encoded_inputs(rounds, n_auth, n_inc, n_vr, with_tx, epoch)
+    res = engine.encode_blocks(heads, includes, payloads, seal=True, link=True,
+                               seeds=np.frombuffer(b"".join(seeds), dtype=np.uint8).reshape(n_auth, 32))
+    if res.status.any() or res.seal_status.any():
+        raise RuntimeError(f"encode_blocks left {int(np.count_nonzero(res.status | res.seal_status))} blocks unsealed")
+    raw = res.buf.tobytes()
+    return [raw[int(o): int(o) + int(l)] for o, l in zip(res.offs, res.lens)]
+
+
 def config1(engine, rounds: int) -> List[bytes]:
     """Config 1: 4 authorities, all with the zero seed (dummy_signer, crypto.rs:355-357)."""
     return build_rounds(engine, rounds, 4, [bytes(32)] * 4, n_inc=4, n_vr=0, with_tx=False)

@@ -785,6 +785,7 @@ void mv_destroy(mv_ctx* ctx) {
     mvr::reset(dev.frm);
     mvr::reset(dev.index);
     mvr::reset(dev.seal);
+    mvr::reset(dev.encode);
     mvr::reset(dev.votes);
     watch.phase("frees: batch and single path");
     mvr::reset(dev.batch);

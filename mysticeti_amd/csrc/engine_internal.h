@@ -2,7 +2,7 @@
 // error plumbing, the sharding helpers, and the declarations of the functions that cross files
 // (engine.cpp, engine_blocks.cpp, engine_online.cpp, engine_wal.cpp, engine_frames.cpp,
 // engine_index.cpp, engine_connect.cpp, engine_dag.cpp, engine_decide.cpp, engine_linearize.cpp,
-// engine_propose.cpp, engine_seal.cpp, engine_votes.cpp).
+// engine_propose.cpp, engine_seal.cpp, engine_encode.cpp, engine_votes.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -240,6 +240,20 @@ struct Device {
     DevBuf keys, heads, tab, md, bd, in, ol, st, seeds;
     HostBuf h;
   } seal;
+
+  // mv_encode_blocks (encode.hip): the per-payload results of the check and the scan of their
+  // bodies, the statement count per block, the list of the large blocks, the scans' per-workgroup words, the control words and
+  // their pinned copy; the inputs and outputs of host-buffer calls (heads, include rows, payload
+  // bytes, payload off | len, the image, out_off | out_len, status, seal status). `done` is
+  // recorded behind every device-buffer call (whose bytes are written after it returned): the next
+  // call's stream waits for it, and it guards the scratch when it grows.
+  struct Encode {
+    DevBuf pay_ok, pay_count, pay_body, pre, blk_count, big, wg, ctl;
+    HostBuf h_ctl;
+    DevBuf heads, inc, pay, pol, out, ool, st, sst;
+    mvr::Event done;
+    bool done_set = false;
+  } encode;
 
   // mv_aggregate_votes (votes.hip): the store -- its own table, the slot -> row map, the rows and
   // the cell arena, made by mv_votes_reserve only; growing and reclaiming fill a fresh copy and
@@ -561,6 +575,13 @@ mv_status linear_marks_for(mv_ctx* ctx, Device& dev, uint64_t old_slots, const m
 using Propose = Device::Index::Propose;
 mv_status propose_follow_table(mv_ctx* ctx, Device& dev, uint64_t old_slots, const mvk::IndexTable& nt, hipStream_t s);
 mv_status propose_clear(mv_ctx* ctx, Device& dev, hipStream_t s);
+
+// engine_seal.cpp: one seal call on device arrays, on stream s, which it synchronises (d_md / d_bd may
+// be null); mv_encode_blocks seals its image through it
+constexpr uint32_t kMaxSealAuth = 1u << 20;
+mv_status seal_run(mv_ctx* ctx, Device& dev, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_off,
+                   const uint64_t* d_len, uint32_t n, const uint8_t* d_seeds, uint32_t n_auth, uint32_t flags,
+                   uint8_t* d_status, uint8_t* d_md, uint8_t* d_bd, hipStream_t s);
 
 // engine_online.cpp
 bool online_eligible(mv_ctx* ctx, uint32_t n, uint64_t bytes, uint64_t longest);

@@ -12,7 +12,6 @@ using namespace mvi;
 
 namespace {
 
-constexpr uint32_t kMaxSealAuth = 1u << 20;
 constexpr uint64_t kNoHead = ~0ull;
 
 // The table of a linked call from the scan's heads (2 words per block: authority, round; all
@@ -56,8 +55,10 @@ mv_status wipe_keys(mv_ctx* ctx, Device::Seal& q, hipStream_t s) {
   return MV_OK;
 }
 
+}  // namespace
+
 // One call on device arrays, on stream s, which it synchronises. d_md / d_bd may be null.
-mv_status seal_run(mv_ctx* ctx, Device& dev, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_off,
+mv_status mvi::seal_run(mv_ctx* ctx, Device& dev, uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_off,
                    const uint64_t* d_len, uint32_t n, const uint8_t* d_seeds, uint32_t n_auth, uint32_t flags,
                    uint8_t* d_status, uint8_t* d_md, uint8_t* d_bd, hipStream_t s) {
   Device::Seal& q = dev.seal;
@@ -110,6 +111,8 @@ mv_status seal_run(mv_ctx* ctx, Device& dev, uint8_t* d_buf, uint64_t buf_bytes,
                                        dev.tab.btab.p, st, d_status, d_md, d_bd, s));
   return wipe_keys(ctx, q, s);  // (its synchronise also ends the copy of t.slots, which is pageable)
 }
+
+namespace {
 
 bool seal_args_ok(const void* buf, const void* off, const void* len, uint32_t n, const void* seeds, uint32_t n_auth,
                   uint32_t flags, const void* status) {

@@ -943,4 +943,44 @@ hipError_t launch_votes_blockout(const VoteCall& c, uint64_t* blk_counts, hipStr
 hipError_t launch_votes_stats(const VoteStore& v, uint64_t nrows, uint64_t* ctl, hipStream_t s);
 // the rows of v with an aggregating cell into q (empty, zeroed); ctl[VT_CTL_NROWS / _NCELLS] = what q holds
 hipError_t launch_votes_move(const VoteStore& v, uint64_t nrows, const VoteStore& q, uint64_t* ctl, hipStream_t s);
+
+// encode.hip: mv_encode_blocks (the bincode of Core::try_new_block's block; rules: encode_walk.h).
+// One call: the caller's arrays, the per-payload results of the check (p entries each; pre p + 1:
+// the exclusive scan of the body lengths and their total, modulo 2^64 -- a block that is OK has a
+// body below MV_ENCODE_MAX_LEN, so the difference of two entries of its run is exact), the
+// statement count per block, and the outputs.
+struct EncodeCall {
+  const uint64_t* heads;
+  uint32_t n;
+  const uint64_t* includes;
+  uint64_t m;
+  const uint8_t* payload_buf;
+  uint64_t payload_bytes;
+  const uint64_t *payload_off, *payload_len;
+  uint64_t p;
+  uint8_t* pay_ok;
+  uint64_t *pay_count, *pay_body, *pre;
+  uint64_t* blk_count;
+  uint32_t* big;  // the blocks of at least EN_WG_BYTES, in block order (n entries of room)
+  uint8_t* out;
+  uint64_t cap;
+  uint64_t *out_off, *out_len;
+  uint8_t* status;
+};
+// control words: the scan of the bodies, the span of the blocks, the failed bounds checks
+// (the words before EN_CTL_ERR are zeroed by every call; that one outlives a call, engine_encode.cpp)
+constexpr int EN_CTL_BODY = 0, EN_CTL_TOTAL = 1, EN_CTL_NBIG = 2, EN_CTL_ERR = 3, EN_CTL_WORDS = 4;
+// a block of at least this many bytes is written by a workgroup, a shorter one by a wave
+constexpr uint64_t EN_WG_BYTES = 4096;
+// a block of at most this many payloads keeps its piece boundaries in LDS
+constexpr uint32_t EN_TILE = 512;
+// k_en_check and the scan of the bodies: pay_ok, pay_count, pay_body, pre; wg: wg_scan_bytes(max(n, p))
+hipError_t launch_encode_check(const EncodeCall& c, void* wg, uint64_t* ctl, hipStream_t s);
+// k_en_size and the scan of the padded lengths: status, out_len, blk_count, out_off, big; ctl[EN_CTL_TOTAL],
+// ctl[EN_CTL_NBIG] = the entries of big
+hipError_t launch_encode_size(const EncodeCall& c, void* wg, uint64_t* ctl, hipStream_t s);
+// k_en_write: the bytes of the OK blocks and their padding (the caller has held ctl[EN_CTL_TOTAL]
+// against cap). A wave per block, unless all nbig = ctl[EN_CTL_NBIG] blocks are large; a workgroup per
+// entry of big, if there is one.
+hipError_t launch_encode_write(const EncodeCall& c, uint64_t nbig, uint64_t* ctl, hipStream_t s);
 }  // namespace mvk

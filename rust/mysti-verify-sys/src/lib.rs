@@ -84,6 +84,13 @@ pub const MV_SEAL_PARSE_ERROR: u8 = 1;
 pub const MV_SEAL_UNKNOWN_AUTHOR: u8 = 2;
 pub const MV_SEAL_UNLINKED: u8 = 3;
 pub const MV_SEAL_LINK: u32 = 1;
+pub const MV_ENCODE_OK: u8 = 0;
+pub const MV_ENCODE_BAD_HEAD: u8 = 1;
+pub const MV_ENCODE_BAD_PAYLOAD: u8 = 2;
+pub const MV_ENCODE_TOO_LONG: u8 = 3;
+pub const MV_ENCODE_MAX_LEN: u64 = 8388600;
+pub const MV_ENCODE_SEAL: u32 = 1;
+pub const MV_ENCODE_LINK: u32 = 2;
 pub const MV_VOTES_OK: u8 = 0;
 pub const MV_VOTES_PARSE_ERROR: u8 = 1;
 pub const MV_VOTES_UNKNOWN_AUTHOR: u8 = 2;
@@ -223,6 +230,18 @@ extern "C" {
                               d_len: *const u64, n: u32, d_seeds: *const u8, n_auth: u32, flags: u32,
                               d_status: *mut u8, d_msg_digest: *mut u8, d_block_digest: *mut u8,
                               stream: *mut c_void) -> i32;
+    pub fn mv_encode_blocks(ctx: *mut mv_ctx, heads: *const u64, n: u32, includes: *const u64, m: u64,
+                            payload_buf: *const u8, payload_bytes: u64, payload_off: *const u64,
+                            payload_len: *const u64, p: u64, flags: u32, seeds: *const u8, n_auth: u32,
+                            out: *mut u8, cap: u64, out_off: *mut u64, out_len: *mut u64, status: *mut u8,
+                            out_bytes: *mut u64, seal_status: *mut u8, msg_digest: *mut u8,
+                            block_digest: *mut u8) -> i32;
+    pub fn mv_dev_encode_blocks(ctx: *mut mv_ctx, device: i32, d_heads: *const u64, n: u32, d_includes: *const u64,
+                                m: u64, d_payload_buf: *const u8, payload_bytes: u64, d_payload_off: *const u64,
+                                d_payload_len: *const u64, p: u64, flags: u32, d_seeds: *const u8, n_auth: u32,
+                                d_out: *mut u8, cap: u64, d_out_off: *mut u64, d_out_len: *mut u64,
+                                d_status: *mut u8, out_bytes: *mut u64, d_seal_status: *mut u8,
+                                d_msg_digest: *mut u8, d_block_digest: *mut u8, stream: *mut c_void) -> i32;
     pub fn mv_votes_reserve(ctx: *mut mv_ctx, blocks: u64, cells: u64) -> i32;
     pub fn mv_votes_clear(ctx: *mut mv_ctx) -> i32;
     pub fn mv_votes_stats(ctx: *mut mv_ctx, out: *mut u64) -> i32;
