@@ -36,6 +36,9 @@
  *                          the DAG store: what BlockStore::open with add_unloaded (block_store.rs:398-404)
  *                          leaves for BaseCommitter to read after a restart
  *   mv_wal_layout          WalWriter::writev position arithmetic (wal.rs:150-188), host only
+ *   mv_wal_write           WalWriter::writev itself for n entries (wal.rs:150-188, 211-216): positions, crc32
+ *                          headers, padding and bodies, as BlockWriter::insert_block and
+ *                          OwnBlockData::write_to_wal use it (block_store.rs:504-518, 542-549)
  *   mv_frame_blocks        the block byte strings of received NetworkMessage frames
  *                          (Network::handle_read_stream, network.rs:400-447), host only
  *   mv_verify_frames       what a connection does with its received bytes, per message: the frame
@@ -322,6 +325,43 @@ mv_status mv_wal_replay(mv_ctx* ctx, const uint8_t* wal, uint64_t size, uint64_t
  * the writer position after them. */
 uint64_t mv_wal_layout(const uint64_t* payload_len, uint64_t n, uint32_t map_bits, uint64_t start,
                        uint64_t* pos /* n */);
+
+/* The WAL write: the bytes WalWriter::writev appends for n entries (wal.rs:150-188: the crc32 of the
+ * payload, the 16-byte header of combine_header, wal.rs:211-216, and the zero padding of an entry
+ * that would straddle a map), as BlockWriter::insert_block and OwnBlockData::write_to_wal call it
+ * for every processed block and for the own block (block_store.rs:504-518, 542-549). The inverse of
+ * mv_wal_replay: a caller appends out[0 .. *end_pos - start) to its file with one pwrite in place of
+ * n write_vectored calls.
+ *
+ * entries: n rows of 4 uint64_t words, mirroring the replay's block rows:
+ *   [0] tag (its low 32 bits; opaque, the writer does not judge it)
+ *   [1] offset of the payload in buf   [2] its length   [3] OwnBlockData::next_entry
+ * For tag 3 (WAL_ENTRY_OWN_BLOCK) the eight little-endian bytes of word [3] are written in front of
+ * the payload and are covered by the crc and by len: what writev(WAL_ENTRY_OWN_BLOCK, &[header,
+ * block]) produces. For every other tag word [3] is ignored. A zero-length payload is an entry
+ * (len 16, crc 0). start = the writer position before the call (WalWriter::pos, at most 2^62);
+ * maps of 2^map_bits bytes, 8 <= map_bits <= 30, as mv_wal_verify.
+ *
+ * out[0 .. *end_pos - start): exactly the bytes write_vectored appends to a file of length `start`
+ * -- per entry the zero gap if the entry would straddle a map (wal.rs:164-172; written as zero
+ * whatever out held), the header combine_header(crc, len, tag).to_le_bytes() with len = body + 16
+ * and crc = crc32fast::hash(body) as a u64, then the body. No byte at or past *end_pos - start is
+ * touched. pos[i] = the WalPosition.start of entry i (what insert_block stores in the index; the
+ * positions are mv_wal_layout's), *end_pos = the writer position after the call.
+ *
+ * Decided before any byte of out is written: MV_E_INVALID_ARG, with out untouched and *end_pos =
+ * start, for a body longer than 2^map_bits - 16 (the assert of wal.rs:153) and for a payload that
+ * leaves buf[0, buf_bytes). If *end_pos - start exceeds cap no byte of out is written, but pos and
+ * *end_pos are: call again with room (the rule of mv_encode_blocks). cap may be 0 and out NULL to
+ * size only; n may be 0 (*end_pos = start). buf and out do not overlap.
+ * Cost: the bytes are written by one wave per entry; the positions take one scan and then one
+ * dependent search per map the image touches, resolved one after another by a single wave while
+ * the call holds the context -- time proportional to (*end_pos - start) / 2^map_bits on top of the
+ * scan (a few steps at map_bits 24; at map_bits 8 about one per entry, which only test sizes bear).
+ * Runs on the context's first device; takes the context in turn. */
+mv_status mv_wal_write(mv_ctx* ctx, const uint8_t* buf, uint64_t buf_bytes, const uint64_t* entries /* n x 4 */,
+                       uint64_t n, uint64_t start, uint32_t map_bits, uint8_t* out, uint64_t cap,
+                       uint64_t* pos /* n */, uint64_t* end_pos);
 
 /* Host-only helper: the Data<StatementBlock> byte strings inside received network frames
  * (Network::handle_read_stream, network.rs:400-447: a u32 big-endian size, then
@@ -1047,6 +1087,18 @@ mv_status mv_dev_wal_replay(mv_ctx* ctx, int device, const uint8_t* d_wal, uint6
                             uint64_t cap, uint64_t* count, uint64_t* d_blk_rows, uint8_t* d_blk_status,
                             uint64_t cap_blocks, uint64_t* n_blocks, uint64_t* d_summary, uint64_t* d_last_seen,
                             void* stream);
+/* mv_wal_write with every array in HBM of the context's first device (MV_E_NO_DEVICE for another);
+ * *end_pos is written on the host. Payload offsets, lengths and `start` are arbitrary bytes: source
+ * and destination need no common alignment. d_buf and d_out follow the block path's contract
+ * (mv_dev_verify_blocks): 8-byte aligned, 16 readable bytes past buf_bytes, and the payloads are read
+ * where mv_dev_connect_blocks, mv_dev_encode_blocks and mv_dev_seal_blocks leave their blocks -- the
+ * offsets and lengths of those calls go into the rows as they are. d_entries and d_pos are 8-byte
+ * aligned (MV_E_INVALID_ARG for a misaligned pointer). Synchronises `stream` once, for the checks
+ * and the total, like mv_dev_encode_blocks; the bytes are then enqueued behind it, and a bounds
+ * check that fails in them is MV_E_HIP from the next WAL write. */
+mv_status mv_dev_wal_write(mv_ctx* ctx, int device, const uint8_t* d_buf, uint64_t buf_bytes,
+                           const uint64_t* d_entries /* n x 4 */, uint64_t n, uint64_t start, uint32_t map_bits,
+                           uint8_t* d_out, uint64_t cap, uint64_t* d_pos /* n */, uint64_t* end_pos, void* stream);
 /* mv_verify_frames on received bytes already in HBM (handle_read_stream, the NetworkMessage decode
  * and process_blocks as there: network.rs:400-457, net_sync.rs:314-383): d_buf, d_soff, d_slen
  * and every output array are device memory; *n_msgs and *n_blocks are written on the host.

@@ -20,6 +20,10 @@ Reference interfaces mirrored (hrubaanna/mysticeti @ 2025-02-04):
   Engine.wal_iter_until    the same as the reference's iterator: (pos, (tag, bytes)), raising
                            where the reference panics
   wal_layout               WalWriter::writev positions (wal.rs:150-188)
+  Engine.wal_write (and dev_wal_write)
+                           WalWriter::writev for many entries (wal.rs:150-188, 211-216), as
+                           BlockWriter::insert_block and OwnBlockData::write_to_wal use it
+                           (block_store.rs:504-518, 542-549): the appended bytes and the positions
   Engine.verify_frames_messages
                            what a connection does with its received bytes, per message:
                            handle_read_stream + the NetworkMessage decode (network.rs:400-457) and
@@ -54,6 +58,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
 import os
 from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
@@ -90,6 +95,7 @@ EXPORTS = [
     "mv_propose_reserve", "mv_propose_add", "mv_dev_propose_add", "mv_propose_take", "mv_propose_own", "mv_propose_stats",
     "mv_seal_blocks", "mv_dev_seal_blocks", "mv_encode_blocks", "mv_dev_encode_blocks",
     "mv_votes_reserve", "mv_votes_clear", "mv_votes_stats", "mv_aggregate_votes", "mv_dev_aggregate_votes",
+    "mv_wal_write", "mv_dev_wal_write",
     "mv_wal_replay", "mv_dev_wal_replay", "mv_dev_crc32", "mv_host_alloc", "mv_host_free", "mv_online_stats", "mv_set_option", "mv_get_option",
 ]
 # per-block outcomes of mv_seal_blocks, and its flag
@@ -254,6 +260,8 @@ def load_library(path: str = LIB_PATH):
     lib.mv_wal_verify.argtypes = [vp, vp, u64, u64, u32, vp, vp, vp, vp, u64, vp]
     lib.mv_wal_layout.argtypes = [vp, u64, u32, u64, vp]
     lib.mv_wal_layout.restype = u64
+    lib.mv_wal_write.argtypes = [vp, vp, u64, vp, u64, u64, u32, vp, u64, vp, vp]
+    lib.mv_dev_wal_write.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, u64, u32, vp, u64, vp, vp, vp]
     lib.mv_frame_blocks.argtypes = [vp, u64, vp, vp, u64, vp]
     lib.mv_frame_blocks.restype = ctypes.c_int64
     lib.mv_frame_messages.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, vp]
@@ -928,6 +936,66 @@ class Engine:
             ptr(d_last_seen), ctypes.c_void_p(stream_handle or None)), "mv_dev_wal_replay")
         return cnt.value, nb.value
 
+    # ---- the WAL write (wal.rs:150-188, block_store.rs:504-518, 542-549) ----
+    def wal_write(self, entries, start: int = 0, map_bits: int = WAL_MAP_BITS, cap: Optional[int] = None,
+                  out: Optional[np.ndarray] = None) -> "WalWrite":
+        """The bytes WalWriter::writev appends for these entries to a file of length `start`
+        (mv_wal_write). entries: (tag, bytes), or (3, next_entry, bytes) for an own block; or a
+        tuple (buf, rows) of the payload bytes and (n, 4) uint64 rows tag | offset | length |
+        next_entry. cap: the room for the bytes (default: what the entries need, from wal_layout);
+        out: a uint8 array to write into (cap = its size). Returns a WalWrite; when end_pos - start
+        exceeds cap its image is empty and nothing was written. Raises MvError with code
+        E_INVALID_ARG for a body no map holds and for a payload outside buf."""
+        if isinstance(entries, tuple):
+            buf = np.ascontiguousarray(entries[0], dtype=np.uint8)
+            rows = np.ascontiguousarray(entries[1], dtype=np.uint64).reshape(-1, 4)
+        else:
+            parts, rows, off = [], np.zeros((len(entries), 4), dtype=np.uint64), 0
+            for i, e in enumerate(entries):
+                tag, nxt, data = (e[0], 0, e[1]) if len(e) == 2 else e
+                rows[i] = (tag, off, len(data), nxt)
+                parts.append(bytes(data))
+                off += len(data)
+            buf = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        n = rows.shape[0]
+        if out is not None:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and
+                    out.flags.writeable):
+                raise ValueError("out: a writable contiguous uint8 array")
+            cap = out.shape[0] if cap is None else int(cap)
+            if cap > out.shape[0]:
+                raise ValueError("cap reaches past out")
+        else:
+            if cap is None:
+                body = rows[:, 2] + np.where((rows[:, 0] & np.uint64(0xFFFFFFFF)) == 3, 8, 0).astype(np.uint64)
+                cap = wal_layout(body, map_bits, int(start))[1] - int(start)
+            out = np.zeros(int(cap), dtype=np.uint8)
+        pos = np.zeros(max(n, 1), dtype=np.uint64)
+        end = ctypes.c_uint64(0)
+        self._check(self.lib.mv_wal_write(self.ctx, _p(buf) if buf.shape[0] else None, buf.shape[0],
+                                          _p(rows) if n else None, n, int(start), map_bits, _p(out) if cap else None,
+                                          int(cap), _p(pos), ctypes.byref(end)), "mv_wal_write")
+        span = end.value - int(start)
+        return WalWrite(out[:span] if span <= cap else out[:0], pos[:n], end.value)
+
+    def dev_wal_write(self, device: int, d_buf, buf_bytes: int, d_entries, start: int, map_bits: int, d_out, cap: int,
+                      d_pos, stream_handle: int = 0) -> int:
+        """mv_dev_wal_write on torch device tensors (d_buf uint8, 8-byte aligned with 16 readable
+        bytes past buf_bytes -- the buffer of a dev_encode_blocks, dev_seal_blocks or
+        dev_connect_blocks call as it is; d_entries (n, 4) int64 rows; d_out uint8 of at least cap
+        bytes; d_pos int64 of n). Synchronises the stream once; returns end_pos. When end_pos - start
+        exceeds cap only d_pos was written."""
+        vp = ctypes.c_void_p
+
+        def ptr(t):
+            return vp(t.data_ptr()) if t is not None and t.numel() else None
+
+        end = ctypes.c_uint64(0)
+        self._check(self.lib.mv_dev_wal_write(self.ctx, device, ptr(d_buf), int(buf_bytes), ptr(d_entries),
+                                              d_entries.shape[0], int(start), map_bits, ptr(d_out), int(cap), ptr(d_pos),
+                                              ctypes.byref(end), vp(stream_handle or None)), "mv_dev_wal_write")
+        return end.value
+
     def dev_crc32(self, device: int, d_buf, d_off, d_len, n: int, d_out, stream_handle: int = 0):
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         self._check(self.lib.mv_dev_crc32(self.ctx, device, ptr(d_buf), ptr(d_off), ptr(d_len), n, ptr(d_out),
@@ -1590,6 +1658,16 @@ class Committed(Decided):
         """The decided rows, in order: (row, status)."""
         rows = [i for i in range(self.leaders.shape[0]) if int(self.leaders[i, 1]) > 0][:self.n_sequence]
         return [(i, int(self.status[i])) for i in rows]
+
+
+@dataclasses.dataclass
+class WalWrite:
+    """Result of Engine.wal_write (include/mysti_verify.h, mv_wal_write). image: the bytes to append
+    at the writer position the call was given (uint8; empty when they did not fit the cap); pos: the
+    WalPosition.start of every entry; end_pos: the writer position after them."""
+    image: np.ndarray
+    pos: np.ndarray
+    end_pos: int
 
 
 class WalReplay:

@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, "libmysti_verify.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
-SOURCES = ["kernels.hip", "batch.hip", "comb.hip", "ingest.hip", "blake2b_quad.hip", "blake2b_lane.hip", "block_walk.hip", "wal.hip", "replay.hip", "frames.hip", "index.hip", "pending.hip", "dag_store.hip", "decide.hip", "linearize.hip", "propose.hip", "seal.hip", "encode.hip", "votes.hip", "engine.cpp",
+SOURCES = ["kernels.hip", "batch.hip", "comb.hip", "ingest.hip", "blake2b_quad.hip", "blake2b_lane.hip", "block_walk.hip", "wal.hip", "wal_write.hip", "replay.hip", "frames.hip", "index.hip", "pending.hip", "dag_store.hip", "decide.hip", "linearize.hip", "propose.hip", "seal.hip", "encode.hip", "votes.hip", "engine.cpp",
            "engine_blocks.cpp", "engine_online.cpp", "engine_wal.cpp", "engine_frames.cpp", "engine_index.cpp", "engine_connect.cpp", "engine_dag.cpp", "engine_decide.cpp", "engine_linearize.cpp", "engine_propose.cpp", "engine_seal.cpp", "engine_encode.cpp", "engine_votes.cpp",
            "block_codec.cpp"]
 # per-source compiler flags of the product build (rust/mysti-verify-sys/build.rs mirrors them):
@@ -29,7 +29,7 @@ SOURCES = ["kernels.hip", "batch.hip", "comb.hip", "ingest.hip", "blake2b_quad.h
 SOURCE_FLAGS = {"batch.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "blake2b_lane.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "ingest.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-HEADERS = ["asm_ops.h", "fe25519.h", "ge25519.h", "hash_dev.h", "scalar25519.h", "kernels.h", "block_codec.h", "tables.h", "carry32.h", "comb.h", "quad25519.h", "fe_q4.h", "fe_r16.h", "blake2b_quad.h", "block_verdict.h", "bincode_walk.h", "ingest_dev.h", "ingest_lane.h", "votes_walk.h", "encode_walk.h", "pt_r16.h", "frame_walk.h", "wal_entry.h", "block_ref.h", "index_dev.h", "dev_resources.h", "engine_internal.h"]
+HEADERS = ["asm_ops.h", "fe25519.h", "ge25519.h", "hash_dev.h", "scalar25519.h", "kernels.h", "block_codec.h", "tables.h", "carry32.h", "comb.h", "quad25519.h", "fe_q4.h", "fe_r16.h", "blake2b_quad.h", "block_verdict.h", "bincode_walk.h", "ingest_dev.h", "ingest_lane.h", "votes_walk.h", "encode_walk.h", "pt_r16.h", "frame_walk.h", "wal_entry.h", "wal_crc.h", "wal_layout.h", "block_ref.h", "index_dev.h", "dev_resources.h", "engine_internal.h"]
 
 
 def _newer(target: str, deps) -> bool:

@@ -158,6 +158,9 @@ struct Device {
     // mv_wal_replay (replay.hip): control words, per-workgroup scans and the block lists, the
     // block rows, and the summary / last_seen of host-buffer calls
     DevBuf rctl, rscr, rows, rsum;
+    // mv_wal_write (wal_write.hip): the sums, the crossing table, the per-workgroup scan and the
+    // control words; payload bytes, entry rows, image and positions of host-buffer calls
+    DevBuf wsum, wcross, wwg, wctl, wbuf, went, wout, wpos;
   } wal;
 
   // mv_verify_frames (frames.hip): per-stream and per-frame walk arrays, the row and block

@@ -1,11 +1,13 @@
 // libmysti_verify.so: the WAL calls -- the entry walk and crc check, the replay up to the block-store
-// index on top of them -- and the crc32 calls (they share the WAL path's crc tables).
+// index on top of them, the write of new entries -- and the crc32 calls (they share the WAL path's
+// crc tables).
 #include <string.h>
 
 #include <algorithm>
 
 #include "engine_internal.h"
 #include "wal_entry.h"
+#include "wal_layout.h"
 
 using namespace mvi;
 
@@ -359,15 +361,134 @@ mv_status mv_dev_wal_replay(mv_ctx* ctx, int device, const uint8_t* d_wal, uint6
 
 uint64_t mv_wal_layout(const uint64_t* payload_len, uint64_t n, uint32_t map_bits, uint64_t start, uint64_t* pos) {
   if (!wal_args_ok(map_bits) || (n && (!payload_len || !pos))) return start;
-  const uint64_t mask = ~((1ull << map_bits) - 1);
   uint64_t p = start;
   for (uint64_t i = 0; i < n; i++) {
-    const uint64_t len = payload_len[i] + 16;  // header + payload (wal.rs:152)
-    if ((p & mask) != ((p + len - 1) & mask)) p = (p + len - 1) & mask;  // zero padding (wal.rs:163-167)
+    const uint64_t len = payload_len[i] + mv::wl::HEADER;  // header + payload (wal.rs:152)
+    p = mv::wl::entry_pos(p, len, map_bits);               // zero padding (wal.rs:163-167)
     pos[i] = p;
     p += len;
   }
   return p;
+}
+
+// ---------------------------------------------------------------- WAL write
+namespace {
+constexpr uint64_t kMaxWalEntries = 0xffffffffull;
+
+bool wal_write_args_ok(const void* buf, uint64_t buf_bytes, const void* entries, uint64_t n, uint64_t start,
+                       uint32_t map_bits, const void* out, uint64_t cap, const void* pos, const void* end_pos) {
+  return end_pos && wal_args_ok(map_bits) && !(buf_bytes && !buf) && !(n && (!entries || !pos)) && !(cap && !out) &&
+         n <= kMaxWalEntries && start <= (1ull << 62) && buf_bytes <= ~0ull - 64 && cap <= ~0ull - 64;
+}
+
+// One call on device arrays (c: the caller's, the scratch is filled in here), on stream s: the
+// layout, its control words read back (the one synchronise), then -- if nothing was refused and the
+// span fits cap -- the bytes, enqueued. *end_pos = c.start where the call is refused.
+mv_status wal_write_run(mv_ctx* ctx, Device& dev, mvk::WalWriteCall c, hipStream_t s, uint64_t* end_pos) {
+  *end_pos = c.start;
+  if (c.n == 0) return MV_OK;
+  mv_status st = wal_tables(ctx, dev);
+  if (st != MV_OK) return st;
+  Device::Wal& q = dev.wal;
+  const bool fresh = !q.wctl.p;
+  HIPCHK(ctx, q.wctl.ensure(8 * mvk::WW_CTL_WORDS));
+  HIPCHK(ctx, q.wsum.ensure(8 * c.n));
+  HIPCHK(ctx, q.wcross.ensure(16 * c.n));
+  HIPCHK(ctx, q.wwg.ensure(mvk::wg_scan_bytes(c.n)));
+  c.sums = q.wsum.as<uint64_t>();
+  c.cross_first = q.wcross.as<uint64_t>();
+  c.cross_shift = c.cross_first + c.n;
+  uint64_t* ctl = q.wctl.as<uint64_t>();
+  // (the byte pass's error word outlives a call: it is reported by the next one)
+  HIPCHK(ctx, hipMemsetAsync(ctl, 0, fresh ? 8 * mvk::WW_CTL_WORDS : 8 * mvk::WW_CTL_ERR, s));
+  HIPCHK(ctx, mvk::launch_wal_write_layout(c, q.wwg.p, ctl, s));
+  uint64_t w[mvk::WW_CTL_WORDS] = {0};
+  HIPCHK(ctx, hipMemcpyAsync(w, ctl, sizeof w, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  if (w[mvk::WW_CTL_ERR]) {
+    HIPCHK(ctx, hipMemsetAsync(ctl + mvk::WW_CTL_ERR, 0, 8, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return set_err(ctx, MV_E_HIP, "wal write: a bounds check failed on the device");
+  }
+  if (w[mvk::WW_CTL_BAD])
+    return set_err(ctx, MV_E_INVALID_ARG, "wal write: a payload leaves buf or a body is longer than a map holds");
+  *end_pos = w[mvk::WW_CTL_END];
+  if (*end_pos - c.start > c.cap) return MV_OK;  // pos and *end_pos are written, no byte of out
+  HIPCHK(ctx, mvk::launch_wal_write_emit(c, q.tab.as<uint32_t>(), ctl, dev.cus, s));
+  return MV_OK;
+}
+}  // namespace
+
+mv_status mv_wal_write(mv_ctx* ctx, const uint8_t* buf, uint64_t buf_bytes, const uint64_t* entries, uint64_t n,
+                       uint64_t start, uint32_t map_bits, uint8_t* out, uint64_t cap, uint64_t* pos, uint64_t* end_pos) {
+  if (!ctx || !wal_write_args_ok(buf, buf_bytes, entries, n, start, map_bits, out, cap, pos, end_pos))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad wal write args");
+  *end_pos = start;
+  if (n == 0) return MV_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device& dev = ctx->devs[0];
+  Device::Wal& q = dev.wal;
+  HIPCHK(ctx, hipSetDevice(dev.id));
+  hipStream_t s = dev.stream;
+  HIPCHK(ctx, q.wbuf.ensure(buf_bytes + 16));
+  HIPCHK(ctx, q.went.ensure(8 * (size_t)mv::wl::ENTRY_WORDS * n));
+  HIPCHK(ctx, q.wpos.ensure(8 * n));
+  if (buf_bytes) HIPCHK(ctx, hipMemcpyAsync(q.wbuf.p, buf, buf_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemsetAsync(q.wbuf.as<uint8_t>() + buf_bytes, 0, 16, s));  // (payloads are read as whole aligned words)
+  HIPCHK(ctx, hipMemcpyAsync(q.went.p, entries, 8 * (size_t)mv::wl::ENTRY_WORDS * n, hipMemcpyHostToDevice, s));
+  mvk::WalWriteCall c{};
+  c.buf = q.wbuf.as<uint8_t>(), c.buf_bytes = buf_bytes;
+  c.entries = q.went.as<uint64_t>(), c.n = n;
+  c.start = start, c.map_bits = map_bits;
+  c.out = nullptr, c.cap = 0;  // the layout first: the image is sized by what it says
+  c.pos = q.wpos.as<uint64_t>();
+  uint64_t end = start;
+  mv_status rc = wal_write_run(ctx, dev, c, s, &end);
+  if (rc != MV_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  const uint64_t span = end - start;
+  if (span && span <= cap) {
+    HIPCHK(ctx, q.wout.ensure(span + 16));
+    c.out = q.wout.as<uint8_t>(), c.cap = span;
+    HIPCHK(ctx, mvk::launch_wal_write_emit(c, q.tab.as<uint32_t>(), q.wctl.as<uint64_t>(), dev.cus, s));
+    HIPCHK(ctx, hipMemcpyAsync(out, c.out, span, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(ctx, hipMemcpyAsync(pos, c.pos, 8 * n, hipMemcpyDeviceToHost, s));
+  uint64_t err = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&err, q.wctl.as<uint64_t>() + mvk::WW_CTL_ERR, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(ctx, hipStreamSynchronize(s));
+  *end_pos = end;
+  if (err) {
+    HIPCHK(ctx, hipMemsetAsync(q.wctl.as<uint64_t>() + mvk::WW_CTL_ERR, 0, 8, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return set_err(ctx, MV_E_HIP, "wal write: a bounds check failed on the device");
+  }
+  return MV_OK;
+}
+
+mv_status mv_dev_wal_write(mv_ctx* ctx, int device, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_entries,
+                           uint64_t n, uint64_t start, uint32_t map_bits, uint8_t* d_out, uint64_t cap, uint64_t* d_pos,
+                           uint64_t* end_pos, void* stream) {
+  if (!ctx || !wal_write_args_ok(d_buf, buf_bytes, d_entries, n, start, map_bits, d_out, cap, d_pos, end_pos))
+    return set_err(ctx, MV_E_INVALID_ARG, "bad wal write args");
+  if (((uintptr_t)d_buf | (uintptr_t)d_entries | (uintptr_t)d_out | (uintptr_t)d_pos) & 7)
+    return set_err(ctx, MV_E_INVALID_ARG, "wal write: misaligned device pointer");
+  *end_pos = start;
+  if (n == 0) return MV_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  Device* dev = find_dev(ctx, device);
+  if (!dev || dev != &ctx->devs[0]) return set_err(ctx, MV_E_NO_DEVICE, "wal write runs on the context's first device");
+  HIPCHK(ctx, hipSetDevice(dev->id));
+  hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)dev->stream;
+  mvk::WalWriteCall c{};
+  c.buf = d_buf, c.buf_bytes = buf_bytes;
+  c.entries = d_entries, c.n = n;
+  c.start = start, c.map_bits = map_bits;
+  c.out = d_out, c.cap = cap;
+  c.pos = d_pos;
+  return wal_write_run(ctx, *dev, c, s, end_pos);
 }
 
 mv_status mv_crc32(mv_ctx* ctx, const uint8_t* buf, const uint64_t* off, const uint64_t* len, uint32_t n,

@@ -983,4 +983,29 @@ hipError_t launch_encode_size(const EncodeCall& c, void* wg, uint64_t* ctl, hipS
 // against cap). A wave per block, unless all nbig = ctl[EN_CTL_NBIG] blocks are large; a workgroup per
 // entry of big, if there is one.
 hipError_t launch_encode_write(const EncodeCall& c, uint64_t nbig, uint64_t* ctl, hipStream_t s);
+
+// wal_write.hip: mv_wal_write (WalWriter::writev for n entries; layout rule: wal_layout.h, crc: wal_crc.h).
+// One call: the caller's arrays and the layout's scratch.
+struct WalWriteCall {
+  const uint8_t* buf;       // the payloads' bytes: 8-byte aligned, 16 readable bytes past buf_bytes
+  uint64_t buf_bytes;
+  const uint64_t* entries;  // n rows: tag | payload offset | payload length | next_entry
+  uint64_t n;
+  uint64_t start;
+  uint32_t map_bits;
+  uint8_t* out;             // cap bytes, 8-byte aligned; byte 0 is writer position `start`
+  uint64_t cap;
+  uint64_t* pos;            // n positions (absolute)
+  uint64_t* sums;           // n: the exclusive sums of the entry lengths
+  uint64_t *cross_first, *cross_shift;  // n each: the step table of the map crossings
+};
+// control words: entries refused (a payload outside buf, a body no map holds) | the writer position
+// after the call | the steps of the crossing table | the sum of the entry lengths | a bounds check of
+// the byte pass failed (it outlives a call: the device-buffer call returns with the bytes enqueued)
+enum { WW_CTL_BAD = 0, WW_CTL_END = 1, WW_CTL_NC = 2, WW_CTL_TOTAL = 3, WW_CTL_ERR = 4, WW_CTL_WORDS = 5 };
+// checks, sums, crossings, pos; ctl[WW_CTL_BAD / _END / _NC / _TOTAL] (zeroed by the caller). wg: wg_scan_bytes(n)
+hipError_t launch_wal_write_layout(const WalWriteCall& c, void* wg, uint64_t* ctl, hipStream_t s);
+// k_ww_emit: gap, header and body of every entry (the caller has held the span against cap and
+// ctl[WW_CTL_BAD] against 0); tables: wal_build_tables'
+hipError_t launch_wal_write_emit(const WalWriteCall& c, const uint32_t* tables, uint64_t* ctl, int cus, hipStream_t s);
 }  // namespace mvk

@@ -8,7 +8,7 @@ use std::path::PathBuf;
 use std::process::Command;
 
 const SOURCES: &[&str] = &[
-    "kernels.hip", "batch.hip", "comb.hip", "ingest.hip", "blake2b_quad.hip", "blake2b_lane.hip", "block_walk.hip", "wal.hip", "replay.hip", "frames.hip", "index.hip", "pending.hip", "dag_store.hip", "decide.hip", "linearize.hip", "propose.hip", "seal.hip", "encode.hip", "votes.hip", "engine.cpp",
+    "kernels.hip", "batch.hip", "comb.hip", "ingest.hip", "blake2b_quad.hip", "blake2b_lane.hip", "block_walk.hip", "wal.hip", "wal_write.hip", "replay.hip", "frames.hip", "index.hip", "pending.hip", "dag_store.hip", "decide.hip", "linearize.hip", "propose.hip", "seal.hip", "encode.hip", "votes.hip", "engine.cpp",
     "engine_blocks.cpp", "engine_online.cpp", "engine_wal.cpp", "engine_frames.cpp", "engine_index.cpp", "engine_connect.cpp", "engine_dag.cpp", "engine_decide.cpp", "engine_linearize.cpp", "engine_propose.cpp", "engine_seal.cpp", "engine_encode.cpp", "engine_votes.cpp",
     "block_codec.cpp",
 ];

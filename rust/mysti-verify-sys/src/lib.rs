@@ -158,6 +158,8 @@ extern "C" {
                           n_blocks: *mut u64, summary: *mut u64, last_seen: *mut u64, floor_round: u64,
                           seeded: *mut u64) -> i32;
     pub fn mv_wal_layout(payload_len: *const u64, n: u64, map_bits: u32, start: u64, pos: *mut u64) -> u64;
+    pub fn mv_wal_write(ctx: *mut mv_ctx, buf: *const u8, buf_bytes: u64, entries: *const u64, n: u64, start: u64,
+                        map_bits: u32, out: *mut u8, cap: u64, pos: *mut u64, end_pos: *mut u64) -> i32;
     pub fn mv_frame_blocks(buf: *const u8, len: u64, off: *mut u64, blen: *mut u64, cap: u64,
                            consumed: *mut u64) -> i64;
     pub fn mv_frame_messages(buf: *const u8, len: u64, msgs: *mut u32, cap_msgs: u64, blk_off: *mut u64,
@@ -275,6 +277,9 @@ extern "C" {
                              d_status: *mut u8, cap: u64, count: *mut u64, d_blk_rows: *mut u64,
                              d_blk_status: *mut u8, cap_blocks: u64, n_blocks: *mut u64,
                              d_summary: *mut u64, d_last_seen: *mut u64, stream: *mut c_void) -> i32;
+    pub fn mv_dev_wal_write(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, buf_bytes: u64, d_entries: *const u64,
+                            n: u64, start: u64, map_bits: u32, d_out: *mut u8, cap: u64, d_pos: *mut u64,
+                            end_pos: *mut u64, stream: *mut c_void) -> i32;
     pub fn mv_dev_crc32(ctx: *mut mv_ctx, device: i32, d_buf: *const u8, d_off: *const u64, d_len: *const u64,
                         n: u32, d_out: *mut u32, stream: *mut c_void) -> i32;
     pub fn mv_batch_stats(ctx: *mut mv_ctx, batches: *mut u64, fallbacks: *mut u64) -> i32;
